@@ -12,6 +12,13 @@ value = whole-job Gauss-Newton iterations per second.
 Driver contract: python bench.py --gpus N --steps K --warmup W.  When launched plainly with N > 1 this
 script re-executes itself under torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1); when
 the driver has already launched it that way (RANK / WORLD_SIZE in the environment) it just runs its rank.
+
+A plain run does only what the headline line needs: generate the windows, upload them, warm up, time the K
+steps and print the line (value, ms_per_step, the job's per-window summary statistics).  --full adds every
+secondary measurement behind the timed steps: the side-rows pass, the PCIe-inclusive protocols, the roofline
+(live rocprofv3 PMC traffic), the single-window latency path, the ceres::Problem surface, the cfg5 stress
+block, the reference-topology configuration, the CPU baseline and the strong-scaling projection.
+--dump-outputs DIR writes what the timed path computed in its last step as float64 .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -388,6 +395,36 @@ def stress_leg(fulls, n_windows, iters):
     return res
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, bs, windows, sms, first, rank, world):
+    """What a caller of the timed path receives from its last step, as float64 .npy files in out_dir: the solved parameter blocks of
+    every window (pose, sb, lm, sc: the windows' blocks concatenated in window order) and the per-window summaries (initial_cost,
+    final_cost, num_iterations, termination); window_index holds the job-wide index of every window written.  The download goes into
+    the windows' host arrays, which get their unsolved values back afterwards, so whatever runs next starts from the same state.
+    Should the batch's outputs exceed 64 MB, a fixed seeded sample of its windows is written instead.  Ranks other than a lone one
+    suffix their files with _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    snap = [w.state() for w in windows]
+    bs.download_state()
+    solved = [w.state() for w in windows]
+    for w, s_ in zip(windows, snap):
+        w.set_state(s_)
+    per_window = [sum(v.nbytes for v in s_.values()) + 5 * 8 for s_ in solved]
+    idx = np.arange(len(windows))
+    if sum(per_window) > DUMP_CAP_BYTES:
+        k = max(1, int(DUMP_CAP_BYTES // max(per_window)))
+        idx = np.sort(np.random.default_rng(20240611).choice(len(windows), size=k, replace=False))
+    arrays = {k: np.concatenate([solved[i][k].ravel() for i in idx]) for k in ("pose", "sb", "lm", "sc")}
+    for k in ("initial_cost", "final_cost", "num_iterations", "termination"):
+        arrays[k] = np.array([getattr(sms[i], k) for i in idx], dtype=np.float64)
+    arrays["window_index"] = (first + idx).astype(np.float64)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def relaunch_under_torchrun(n):
     """python bench.py --gpus N (N > 1) without a launcher: become `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`."""
@@ -418,7 +455,14 @@ def main():
     ap.add_argument("--stress-windows", type=int, default=128, help="windows of the cfg5 stress block (0 = skip it)")
     ap.add_argument("--no-single-window", action="store_true",
                     help="skip the single-window latency leg (its launches share kernel names with the batch and would dilute rocprofv3 per-kernel averages)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every secondary measurement as well (the --no-* options above select among them); "
+                         "without it only the headline line is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64, at most 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         sys.exit(relaunch_under_torchrun(a.gpus))
@@ -436,10 +480,10 @@ def main():
     windows = make_windows(a.config, shard.window_seeds(synth.BASE_SEED, a.config, B, first=first))
     t_gen = time.perf_counter() - t0
     fulls = None
-    if world == 1 and a.stress_windows > 0 and not a.no_single_window and not os.environ.get("SWF_BENCH_SHARE_GPU"):
+    if a.full and world == 1 and a.stress_windows > 0 and not a.no_single_window and not os.environ.get("SWF_BENCH_SHARE_GPU"):
         fulls = stress_fulls(a.stress_windows)
     topo_wxs, topo_err = None, None
-    if world == 1 and not a.no_rtk_topology and not a.no_single_window and not os.environ.get("SWF_BENCH_SHARE_GPU"):
+    if a.full and world == 1 and not a.no_rtk_topology and not a.no_single_window and not os.environ.get("SWF_BENCH_SHARE_GPU"):
         try:                                            # an extra: never take the headline line down with it
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import rtk_topology_gen as rt_gen
@@ -475,31 +519,34 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # warm-up, with every kernel bracketed once to find the dominant one
+    # warm-up (--full: with every kernel bracketed once to find the dominant one)
     bs.reset_state(); bs.solve_async(opt); bs.sync()             # first touch of every buffer, code objects loaded
-    bs.enable_timing(True)
+    if a.full:
+        bs.enable_timing(True)
     for _ in range(max(1, a.warmup)):
         bs.reset_state(); bs.solve_async(opt); bs.sync()
-    calib = bs.timing()
-    kern = {k: v for k, v in calib["kernels"].items() if k != "total"}
-    dom = max(kern, key=lambda k: kern[k]["ms"])
-    from rtk_visual_inertial_navigation_amd.solver import K_NAMES
-    # live HIP-event brackets in the timed region: the whole solve and the DOMINANT kernel (`roofline`).  Every bracket costs the stream two
-    # event packets — ~6 us of idle queue each side of the kernel in the trace, 0.3 ms per 512-window solve with four kernels bracketed as up to
-    # round 5 — so the other rows (the Jacobian evaluation, the second matrix-core kernel) are measured in a pass of their own BEHIND the
-    # timed region, same steps, same inputs (`side_rows_pass` in the line).
-    mask = 1 | (1 << K_NAMES.index(dom))
-    mask_side = 1 | (1 << K_NAMES.index(dom)) | (1 << K_NAMES.index("eval_ps")) | (1 << K_NAMES.index("lm_schur")) | (1 << K_NAMES.index("chol_solve"))
-    bs.enable_timing(mask)
+    if a.full:
+        calib = bs.timing()
+        kern = {k: v for k, v in calib["kernels"].items() if k != "total"}
+        dom = max(kern, key=lambda k: kern[k]["ms"])
+        from rtk_visual_inertial_navigation_amd.solver import K_NAMES
+        # live HIP-event brackets in the timed region: the whole solve and the DOMINANT kernel (`roofline`).  Every bracket costs the stream two
+        # event packets — ~6 us of idle queue each side of the kernel in the trace, 0.3 ms per 512-window solve with four kernels bracketed as up to
+        # round 5 — so the other rows (the Jacobian evaluation, the second matrix-core kernel) are measured in a pass of their own BEHIND the
+        # timed region, same steps, same inputs (`side_rows_pass` in the line).  A plain run brackets nothing.
+        mask = 1 | (1 << K_NAMES.index(dom))
+        mask_side = 1 | (1 << K_NAMES.index(dom)) | (1 << K_NAMES.index("eval_ps")) | (1 << K_NAMES.index("lm_schur")) | (1 << K_NAMES.index("chol_solve"))
+        bs.enable_timing(mask)
 
     barrier()
     t0 = time.perf_counter()
     acc = {}
     for _ in range(a.steps):
         bs.reset_state(); bs.solve_async(opt); bs.sync()
-        t = bs.timing()
-        for k, v in t["kernels"].items():
-            d = acc.setdefault(k, dict(ms=0.0, calls=0)); d["ms"] += v["ms"]; d["calls"] += v["calls"]
+        if a.full:
+            t = bs.timing()
+            for k, v in t["kernels"].items():
+                d = acc.setdefault(k, dict(ms=0.0, calls=0)); d["ms"] += v["ms"]; d["calls"] += v["calls"]
     barrier()
     dt = time.perf_counter() - t0
     dt = shard.allreduce([dt], "max", device=cdev)[0]          # RCCL all-reduce (harness only)
@@ -507,6 +554,38 @@ def main():
     its_total = shard.allreduce([float(sum(s.num_iterations for s in sms))], "sum", device=cdev)[0]
     job = shard.gather_summaries(np.array([[s.final_cost, s.num_iterations, s.termination] for s in sms]), device=cdev)
     value = its_total * a.steps / dt
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, bs, windows, sms, first, rank, world)
+    if rank == 0:
+        out = {
+            # `value`: the timed region starts with the windows' parameter blocks resident in HBM (the bench contract's protocol);
+            # SURVEY.md 8d's host-to-host protocol (upload + solve + download inside the timed region) is `survey_8d_protocol` (--full)
+            "metric": "gauss_newton_iterations_per_sec", "value": value, "unit": "iterations/s",
+            "value_protocol": "inputs resident in HBM when the timed region starts; PCIe-inclusive rates (--full): with_state_upload, survey_8d_protocol",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
+            "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(a.full),
+            "config": {"workload": "BASELINE cfg4: batch of %d independent cfg3 windows (20 keyframes, 300 features, 3000 observations, "
+                                   "19 IMU factors, 10 satellites x 20 epochs carrier-phase+pseudorange, gauge prior) over the job, "
+                                   "%d dogleg iterations per solve" % (job_windows, a.iters),
+                       "windows": job_windows, "windows_rank0": B, "max_num_iterations": a.iters,
+                       "sharding": "independent windows in contiguous blocks, no data-path collective; harness-only all-reduce / all-gather"},
+            "windows_per_sec": job_windows * a.steps / dt,
+            "iterations_per_window": its_total / job_windows,
+            "job_final_cost_mean": float(job[:, 0].mean()), "job_windows": int(job.shape[0]),
+            # terminations 1..4 = converged / iteration limit; anything else (linear solver failure, ...) would make the rate meaningless
+            "job_failed_windows": int(np.sum(~np.isin(job[:, 2].astype(int), (1, 2, 3, 4)))),
+            "setup": {"generate_s": t_gen, "structure_upload_s": t_struct},
+        }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out))
+        bs.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+    if not a.full:
+        return finish()
     # the side rows: the same steps once more with the other kernels of interest bracketed as well (not part of `value`)
     acc_dom = {k: dict(v) for k, v in acc.items()}
     bs.enable_timing(mask_side)
@@ -690,20 +769,7 @@ def main():
             one.close()
             single = dict(us_per_iteration=1e3 * float(np.median(lat)) / max(1, it1), iterations_per_s=max(1, it1) / (1e-3 * float(np.median(lat))),
                           solve_ms_median=float(np.median(lat)), solve_ms_p10=float(np.percentile(lat, 10)), solve_ms_p90=float(np.percentile(lat, 90)))
-        out = {
-            # `value`: the timed region starts with the windows' parameter blocks resident in HBM (the bench contract's protocol);
-            # SURVEY.md 8d's host-to-host protocol (upload + solve + download inside the timed region) is `survey_8d_protocol` below
-            "metric": "gauss_newton_iterations_per_sec", "value": value, "unit": "iterations/s",
-            "value_protocol": "inputs resident in HBM when the timed region starts; PCIe-inclusive rates: with_state_upload, survey_8d_protocol",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
-            "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "BASELINE cfg4: batch of %d independent cfg3 windows (20 keyframes, 300 features, 3000 observations, "
-                                   "19 IMU factors, 10 satellites x 20 epochs carrier-phase+pseudorange, gauge prior) over the job, "
-                                   "%d dogleg iterations per solve" % (job_windows, a.iters),
-                       "windows": job_windows, "windows_rank0": B, "max_num_iterations": a.iters,
-                       "sharding": "independent windows in contiguous blocks, no data-path collective; harness-only all-reduce / all-gather"},
-            "windows_per_sec": job_windows * a.steps / dt,
-            "iterations_per_window": its_total / job_windows,
+        out.update({
             "with_state_upload": {"ms_per_step": 1e3 * dt_up / a.steps, "value": its_total * a.steps / dt_up,
                                   "note": "parameter blocks re-uploaded from the caller's (pageable) memory before every solve, through the batch's page-locked staging buffer (PCIe-inclusive)"},
             "survey_8d_protocol": {"ms_per_step": 1e3 * dt_ud / a.steps, "value": its_total * a.steps / dt_ud,
@@ -711,15 +777,11 @@ def main():
             "side_rows_pass": {"ms_per_step": 1e3 * dt_side / a.steps, "bracketed": ["total", dom, "eval_ps", "lm_schur", "chol_solve"],
                                "note": "the timed region's steps once more with four kernels bracketed by HIP events instead of one (every bracket idles the queue ~6 us either side of its kernel): source of roofline_jacobian and of the second matrix-core row; up to round 5 the timed region itself ran like this"},
             "strong_scaling_projection": proj,
-            "job_final_cost_mean": float(job[:, 0].mean()), "job_windows": int(job.shape[0]),
-            # terminations 1..4 = converged / iteration limit; anything else (linear solver failure, ...) would make the rate meaningless
-            "job_failed_windows": int(np.sum(~np.isin(job[:, 2].astype(int), (1, 2, 3, 4)))),
             "roofline": roof,
             "roofline_jacobian": jac,
             "kernel_ms_per_solve_calibration": {k: v["ms"] for k, v in calib["kernels"].items()},
             "single_window": single,
-            "setup": {"generate_s": t_gen, "structure_upload_s": t_struct},
-        }
+        })
         if not a.no_single_window:
             out["problem_surface"] = structure_change_leg(windows[0].copy(), a.iters)
         if fulls is not None:
@@ -750,11 +812,7 @@ def main():
                 out["single_window"]["speedup_vs_cpu_single_thread"] = cb["single_thread_us_per_iteration"] / single["us_per_iteration"]
                 out["single_window"]["north_star_target_x"] = 20.0
                 out["single_window"]["north_star_target_met"] = bool(lat >= 20.0)
-        print(json.dumps(out))
-    bs.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -148,6 +148,40 @@ def test_bench_eight_ranks_sharing_one_gpu_reports_the_whole_job():
     assert out1["job_windows"] == 20 and out1["job_final_cost_mean"] == out["job_final_cost_mean"]
 
 
+@pytest.mark.gpu
+def test_bench_dumps_the_timed_steps_outputs_in_plain_and_full_runs(tmp_path):
+    """--dump-outputs DIR: the last timed step's solved blocks and per-window summaries as float64 .npy files.  The same arguments give
+    the same inputs, so a plain run and a --full run (whose secondary legs come after the dump) write identical arrays; only --full
+    carries the secondary rows."""
+    import json
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--windows", "16", "--no-cpu-baseline", "--no-live-traffic",
+            "--no-rtk-topology", "--stress-windows", "0"]
+    outs, dumps = [], []
+    for extra in ([], ["--full"]):
+        d = tmp_path / ("full" if extra else "plain")
+        r = _run_bench(args + extra + ["--dump-outputs", str(d)], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        outs.append(json.loads(lines[0]))
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    plain, full = outs
+    for o in outs:
+        assert o["steps"] == 2 and o["ms_per_step"] > 0 and o["value"] > 0 and o["job_windows"] == 16 and o["job_failed_windows"] == 0
+    assert "roofline" not in plain and "with_state_upload" not in plain and "single_window" not in plain
+    assert "roofline" in full and "with_state_upload" in full and full["single_window"] is not None
+    assert plain["job_final_cost_mean"] == full["job_final_cost_mean"]
+    names = {"pose", "sb", "lm", "sc", "initial_cost", "final_cost", "num_iterations", "termination", "window_index"}
+    assert set(dumps[0]) == names and set(dumps[1]) == names
+    assert sum(v.nbytes for v in dumps[0].values()) <= 64 << 20
+    for k in names:
+        assert dumps[0][k].dtype == np.float64
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
+    np.testing.assert_array_equal(dumps[0]["window_index"], np.arange(16))
+    assert dumps[0]["final_cost"].mean() == pytest.approx(plain["job_final_cost_mean"], rel=1e-14)
+    assert dumps[0]["num_iterations"].sum() == plain["iterations_per_window"] * 16
+
+
 def _uneven_worker(rank, world, port, total, out_dir):
     for p in (ROOT, os.path.join(ROOT, "tests")):
         if p not in sys.path:
