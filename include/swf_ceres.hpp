@@ -521,4 +521,18 @@ inline bool UpdateSchurHessianOnly(Problem* p, TailCovariance* out) {
     return rc == SWF_OK && n > 0;
 }
 
+// RTKLIB's lambda(n, m, a, Q, F, s) (R/gnss/src/lambda.cpp:213-235) with its contract — column-major Q (n x n), F n x m, returns 0
+// on success and non-zero otherwise — computed on the device (swf_lambda_batch, one problem; n <= 64, m <= 2).  The reference's
+// LambdaSearch binds to it by qualifying its one call (R/swf/swf_lambda.cpp:201): swf_ceres::lambda(Qb.rows(), 2, b.data(), Qb.data(), F, s).
+inline int lambda(int n, int m, const double* a, const double* Q, double* F, double* s) {
+    if (n <= 0 || m <= 0 || !a || !Q || !F || !s) return -1;
+    const int32_t nn = n;
+    int32_t info = -1;
+    std::vector<double> Fo((size_t)n * m);
+    if (swf_lambda_batch(1, nn, &nn, a, Q, m, Fo.data(), s, &info, 0, nullptr) != SWF_OK) return -1;
+    if (info != SWF_LAMBDA_OK) return info;
+    std::memcpy(F, Fo.data(), Fo.size() * sizeof(double));   // F[(0 * m + j) * n + i] = column j of the n x m matrix
+    return 0;
+}
+
 }  // namespace swf_ceres

@@ -48,6 +48,9 @@ enum {
  * Structural limits of a group-0 clique (a non-landmark block of elimination group 0 with the factors touching it): at most 9 eliminated
  * dimensions d_e, at most 768 columns d = d_e + d_f, and — for cliques beyond one wavefront's 64 x 64 / 96 x 64, which take the
  * workgroup kernel — d_e * d <= 1536 (d <= 170 at d_e = 9, 256 at d_e = 6, 512 at d_e = 3): SWF_E_UNSUPPORTED beyond.
+ * 107: no layout change; the LAMBDA integer ambiguity search on the device: swf_lambda_batch (stand-alone, RTKLIB's lambda() for a batch
+ * of problems) and swf_batch_ambiguity_search / swf_batch_get_ambiguity_fix (LambdaSearch's numeric core after
+ * swf_batch_tail_covariance, ratio test included).
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);
@@ -172,13 +175,37 @@ int swf_batch_get_prior(swf_batch* b, int32_t w, double* A, double* bv, double* 
  *   A  = L_nn L_nn^T   information of the parameter_head states — what SWFOptimization::UpdateSchurHessianOnly forms from
  *                      lhs_out2 (R/swf/swf_gnss.cpp:65-94);
  *   Qy = A^-1          their covariance — what SWFOptimization::LambdaSearch computes next (R/swf/swf_lambda.cpp:94-99) and feeds,
- *                      with the float ambiguities, to the LAMBDA search (which stays on the host: integer least squares is
- *                      sequential and branchy).
+ *                      with the float ambiguities, to the LAMBDA search.  The search runs on the device too:
+ *                      swf_batch_ambiguity_search below takes Qy from here without a host round trip.
  * L is the Cholesky factor of the last linear solve of each window (it includes the dogleg's mu * diag regularisation, as the
  * exported lhs_out2 does).  n_red <= 512.  swf_batch_tail_covariance is asynchronous; the getter synchronises; both matrices
  * are n x n row-major, n = tail dimension; *n = -1 and SWF_E_STATE for a window without a valid factor. */
 int swf_batch_tail_covariance(swf_batch* b);
 int swf_batch_get_tail_covariance(swf_batch* b, int32_t w, double* A, double* Qy, int32_t* n);
+
+/* Integer ambiguity resolution: the numeric core of SWFOptimization::LambdaSearch (R/swf/swf_lambda.cpp:82-365) for every window,
+ * on the device (swf_lambda_batch's kernel with a gather prologue and a ratio-test epilogue).  Needs a swf_batch_tail_covariance
+ * issued after the last solve (SWF_E_STATE otherwise).
+ *   pair_first [n_windows + 1], pairs [pair_first[n_windows]][2]   host arrays: window w owns pairs pair_first[w] ..
+ *             pair_first[w+1]-1; a pair is (tail coordinate of an ambiguity, tail coordinate of its reference ambiguity) — one row
+ *             of the reference's D (:164-166).  An index outside the tail, a == b, or a coordinate of a tail block whose size is not
+ *             1: SWF_E_INVALID; more than SWF_LAMBDA_NMAX pairs in a window: SWF_E_UNSUPPORTED.
+ * Then, asynchronously on the batch stream, per window with n_b pairs:
+ *   Qb = D Qy D^T (n_b x n_b, from the tail covariance), bf = D y (y = the device state of the tail blocks at call time),
+ *   the LAMBDA search with m = 2 (F, s, info as swf_lambda_batch), and the ratio test (:208-253):
+ *     S = {i : |F1_i - F2_i| < 1e-2}, same_cost = e_S^T Qb_SS^-1 e_S with e = F1 - bf, s1' = s[1] - same_cost,
+ *     s0' = s[0] - same_cost (1e-3 when |s0'| < 1e-3), ratio = {s[1] / s[0], s1' / s0'},
+ *     fixed = s[0] <= 0 || ratio[0] >= ratio_threshold || ratio[1] >= ratio_threshold   (the reference's threshold is 2).
+ *   A window without pairs or without a valid tail covariance reports SWF_LAMBDA_NO_INPUT.
+ * The getter synchronises; its first call after a search copies every window's results to the host in one transfer, later calls
+ * read that copy.  Every pointer may be NULL.  F [2][n_b] (candidate j at F[j * n_b + i]), s [2], ratio [2], fixed [1],
+ * Qb [n_b][n_b] row-major and bf [n_b] (the search's own inputs, so that a caller can replay them), n_b, info (SWF_LAMBDA_*).
+ * ratio / fixed are 0 unless info == SWF_LAMBDA_OK.  The search results are invalidated by the next swf_batch_solve
+ * (SWF_E_STATE).  Stays with the caller: the choice of the reference satellites and the fractional-part gating of D's rows (:163),
+ * the early returns on too few rows (:178, :184), the fix counter and the new prior of FixedIntegerFactors (:250-, swf_add_fixed_integer). */
+int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_first, const int32_t* pairs, double ratio_threshold);
+int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, double* s, double* ratio, int32_t* fixed,
+                                double* Qb, double* bf, int32_t* n_b, int32_t* info);
 
 /* Timing of the last swf_batch_solve, measured with HIP events recorded on the batch stream
  * around individual kernel launches (valid after swf_batch_sync).  `mask` selects which
@@ -231,6 +258,25 @@ int swf_batch_timing(swf_batch* b, swf_timing* out);
  * ===================================================================================== */
 int swf_preintegrate_batch(const double* samples, const int32_t* first, int32_t n_intervals, const double* bias,
                            const double noise[4], double* pre, int32_t on_device, void* stream);
+
+/* Integer least squares: RTKLIB's lambda(n, m, a, Q, F, s) (R/gnss/src/lambda.cpp:58-235) for a batch of problems, one wavefront
+ * each: LtDL factorisation, LAMBDA reduction, MLAMBDA search for the m best integer vectors, with the reference's discrete decisions
+ * (ROUND = floor(x + 0.5), the 1e-6 permutation margin, LOOPMAX = 10000 search iterations).  The reduction, unbounded in the
+ * reference, gives up after 100000 permutations; both limits report SWF_LAMBDA_LOOP_LIMIT.  F = Z^-T E is formed from Z^-1 carried
+ * through the reduction as integer row updates: exactly integer-valued.
+ *   n  [n_problems]                 unknowns per problem, 1 <= n <= ld
+ *   a  [n_problems][ld]             float solutions
+ *   Q  [n_problems][ld][ld]         their covariances, column-major (only the lower triangle is read)
+ *   m                               candidates, 1 or 2 (the reference takes 2)
+ *   F  [n_problems][m][ld]          candidate j of problem p at F[(p * m + j) * ld + i] (0 beyond n and on failure)
+ *   s  [n_problems][m]              their squared distances (a - F)^T Q^-1 (a - F), ascending
+ *   info [n_problems]               SWF_LAMBDA_* per problem
+ * ld > 64, m out of range, or (host memory) some n > 64 or n > ld: SWF_E_UNSUPPORTED; null pointers: SWF_E_INVALID.  A problem's
+ * result does not depend on the other problems of the call.  on_device as for swf_preintegrate_batch. */
+#define SWF_LAMBDA_NMAX 64
+enum { SWF_LAMBDA_OK = 0, SWF_LAMBDA_NOT_PD = 1, SWF_LAMBDA_LOOP_LIMIT = 2, SWF_LAMBDA_NO_INPUT = 3 };
+int swf_lambda_batch(int32_t n_problems, int32_t ld, const int32_t* n, const double* a, const double* Q,
+                     int32_t m, double* F, double* s, int32_t* info, int32_t on_device, void* stream);
 
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).

@@ -20,6 +20,7 @@
 #include "swf_kernels2.h"
 #include "swf_kernels3.h"
 #include "swf_kernels4.h"
+#include "swf_lambda.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -27,7 +28,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 extern "C" const char* swf_last_error(void) { return g_err.c_str(); }
 void swf_internal_set_error(const std::string& m) { g_err = m; }
-extern "C" int swf_version(void) { return 106; }
+extern "C" int swf_version(void) { return 107; }
 extern "C" int swf_abi_sizes(int32_t out[5]) {
     if (!out) return fail(SWF_E_INVALID, "swf_abi_sizes: null");
     out[0] = (int32_t)sizeof(swf_options); out[1] = (int32_t)sizeof(swf_summary); out[2] = (int32_t)sizeof(swf_timing);
@@ -200,6 +201,7 @@ struct HostWin {       // what the host keeps per window for state transfer / ex
     int comp_e0 = 0, comp_ne = 0;                       // their range in the batch-wide hidden-epoch arrays
     std::vector<int> p_orig;                            // device observation (proj0 + q) -> the caller's projection factor index
     int n_proj_all = 0;                                 // the caller's projection factors, fast path + generic path (GF_PROJX)
+    std::vector<int> tail_x;                            // per tail coordinate: its state index if its block has size 1, else -1
 };
 
 struct swf_batch {
@@ -227,6 +229,12 @@ struct swf_batch {
     int* mg_rot = nullptr; int* mg_bjok = nullptr; unsigned long long* mg_crit = nullptr;                                       // k_marg_bj: rotations per sweep, windows taking part
     // ambiguity covariance hand-off outputs (allocated at the first swf_batch_tail_covariance)
     int* tc_tail = nullptr; double* tc_A = nullptr; double* tc_Q = nullptr; double* tc_X = nullptr; int* tc_rank = nullptr; bool tc_valid = false; int tc_ld = 0;
+    // integer ambiguity search (allocated at the first swf_batch_ambiguity_search for n_windows x 64 pairs, the most a search may pass):
+    // the pair table and one record of results per window (LBD_REC_*, stride am_rec_ld), mirrored to the host by the first getter
+    int* am_first = nullptr; int4* am_pairs = nullptr; double* am_rec = nullptr; int am_rec_ld = 0;
+    bool am_valid = false, am_host = false; std::vector<double> h_am;
+    std::vector<int> am_nb;                             // pairs per window of the last search
+    std::vector<int> am_h_first; std::vector<int4> am_h_pairs;      // host staging of the pair upload (outlives the asynchronous copy)
     // latency path (small batches): an auxiliary stream runs the IMU / clique branch of a linearisation next to the
     // projection / landmark branch; three reusable events carry the dependencies
     hipStream_t aux = nullptr; hipEvent_t ev_fork[3] = { nullptr, nullptr, nullptr };
@@ -325,7 +333,12 @@ int build_window(Build& B, const swf_flat_window* w, int wi, HostWin& hw) {
     R.Lt_base = B.Lt_tot; B.Lt_tot += (long long)(R.n_red + 1) * (R.n_red + 1);
     {
         int td = 0;
-        for (int i = w->n_order - w->n_tail; i < w->n_order; i++) if (i >= 0) td += ls[w->order_block[i]];
+        hw.tail_x.clear();
+        for (int i = w->n_order - w->n_tail; i < w->n_order; i++) if (i >= 0) {
+            const int b = w->order_block[i];
+            td += ls[b];
+            for (int k = 0; k < ls[b]; k++) hw.tail_x.push_back(gs[b] == 1 ? R.x_base + xo[b] : -1);
+        }
         hw.tail_dim = td; R.tail_dim = td;
     }
     if (nP > CTL_NT) return fail(SWF_E_UNSUPPORTED, "more than 256 pose blocks in a window");      // k_dogleg: a thread per pose block
@@ -1808,7 +1821,7 @@ extern "C" int swf_batch_solve(swf_batch* b, const swf_options* opt) {
     b->last.lm_schur_flops = b->lm_schur_flops; b->last.n_obs = b->D.n_proj;
     b->last.lm_schur_flops_sym = b->lm_schur_flops_sym; b->last.lm_schur_mfma = b->lm_schur_mfma;
     b->last.n_linearizations = nlin;
-    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false;      // consumer outputs belong to the previous solve
+    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false; b->am_valid = false;      // consumer outputs belong to the previous solve
     return SWF_OK;
 }
 
@@ -2100,6 +2113,83 @@ extern "C" int swf_batch_get_tail_covariance(swf_batch* b, int32_t w, double* A,
     if (rk < 0) return fail(SWF_E_STATE, "tail covariance: the window has no valid factor (failed linear solve or empty tail)");
     if (A) HIPCHK(hipMemcpy(A, b->tc_A + o2, n * n * sizeof(double), hipMemcpyDeviceToHost));
     if (Qy) HIPCHK(hipMemcpy(Qy, b->tc_Q + o2, n * n * sizeof(double), hipMemcpyDeviceToHost));
+    return SWF_OK;
+}
+
+// integer ambiguity search (LambdaSearch's numeric core): gather D Qy D^T and D y, LAMBDA with m = 2, ratio test — one k_lambda<true>
+extern "C" int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_first, const int32_t* pairs, double ratio_threshold) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b || !pair_first) return fail(SWF_E_INVALID, "swf_batch_ambiguity_search: null argument");
+    if (!b->tc_valid) return fail(SWF_E_STATE, "swf_batch_ambiguity_search needs a swf_batch_tail_covariance after the last solve");
+    const int nw = (int)b->win.size();
+    if (pair_first[0] != 0) return fail(SWF_E_INVALID, "swf_batch_ambiguity_search: pair_first[0] must be 0");
+    std::vector<int> nb(nw);
+    int nmax = 1;
+    for (int w = 0; w < nw; w++) {
+        nb[w] = pair_first[w + 1] - pair_first[w];
+        if (nb[w] < 0) return fail(SWF_E_INVALID, "swf_batch_ambiguity_search: pair_first must be non-decreasing");
+        if (nb[w] > SWF_LAMBDA_NMAX) return fail(SWF_E_UNSUPPORTED, "swf_batch_ambiguity_search: more than 64 pairs in a window");
+        nmax = std::max(nmax, nb[w]);
+    }
+    const int total = pair_first[nw];
+    if (total > 0 && !pairs) return fail(SWF_E_INVALID, "swf_batch_ambiguity_search: null pairs");
+    std::vector<int4>& pr = b->am_h_pairs;
+    pr.assign((size_t)std::max(total, 1), make_int4(0, 0, 0, 0));
+    for (int w = 0; w < nw; w++) {
+        const HostWin& h = b->hw[w];
+        for (int q = pair_first[w]; q < pair_first[w + 1]; q++) {
+            const int ta = pairs[2 * q], tb = pairs[2 * q + 1];
+            if (ta < 0 || tb < 0 || ta >= h.tail_dim || tb >= h.tail_dim || ta == tb)
+                return fail(SWF_E_INVALID, "swf_batch_ambiguity_search: pair index outside the tail, or a == b (window " + std::to_string(w) + ")");
+            const int xa = h.tail_x[ta], xb = h.tail_x[tb];
+            if (xa < 0 || xb < 0) return fail(SWF_E_INVALID, "swf_batch_ambiguity_search: a pair on a tail block whose size is not 1 (window " + std::to_string(w) + ")");
+            pr[q] = make_int4(ta, tb, xa, xb);
+        }
+    }
+    if (!b->am_rec) {
+        int rc = 0;
+        rc |= b->pool.zeros((size_t)nw + 1, &b->am_first);
+        rc |= b->pool.zeros((size_t)nw * SWF_LAMBDA_NMAX, &b->am_pairs);
+        rc |= b->pool.zeros((size_t)nw * (LBD_REC_QB + SWF_LAMBDA_NMAX * SWF_LAMBDA_NMAX), &b->am_rec);
+        if (rc) return fail(SWF_E_NODEVICE, "device allocation failed");
+    }
+    b->am_h_first.assign(pair_first, pair_first + nw + 1);
+    HIPCHK(hipMemcpyAsync(b->am_first, b->am_h_first.data(), (size_t)(nw + 1) * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    if (total > 0) HIPCHK(hipMemcpyAsync(b->am_pairs, pr.data(), (size_t)total * sizeof(int4), hipMemcpyHostToDevice, b->stream));
+    LambdaArgs A{};
+    A.n_prob = nw; A.ld = SWF_LAMBDA_NMAX; A.m = 2; A.ldl = std::max(1, nmax) | 1;
+    A.pair_first = b->am_first; A.pairs = b->am_pairs;
+    A.tcQ = b->tc_Q; A.tc_ld = b->tc_ld; A.tc_n = b->tc_tail; A.tc_rank = b->tc_rank; A.x = b->D.x;
+    A.rec = b->am_rec; A.rec_ld = LBD_REC_QB + nmax * nmax; A.thr = ratio_threshold;
+    b->am_valid = false;
+    const int rc = swf_internal_lambda_launch(A, true, b->stream);
+    if (rc) return rc;
+    b->am_nb = nb; b->am_rec_ld = A.rec_ld;
+    b->am_valid = true; b->am_host = false;
+    return SWF_OK;
+}
+
+extern "C" int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, double* s, double* ratio, int32_t* fixed,
+                                           double* Qb, double* bf, int32_t* n_b, int32_t* info) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b || w < 0 || w >= (int)b->win.size()) return fail(SWF_E_INVALID, "bad window index");
+    if (!b->am_valid) return fail(SWF_E_STATE, "swf_batch_get_ambiguity_fix before swf_batch_ambiguity_search (or after a new solve)");
+    if (!b->am_host) {          // the first getter after a search copies every window's record in one transfer
+        HIPCHK(hipStreamSynchronize(b->stream));
+        b->h_am.resize((size_t)b->win.size() * b->am_rec_ld);
+        HIPCHK(hipMemcpy(b->h_am.data(), b->am_rec, b->h_am.size() * sizeof(double), hipMemcpyDeviceToHost));
+        b->am_host = true;
+    }
+    const double* r = b->h_am.data() + (size_t)w * b->am_rec_ld;
+    const size_t n = (size_t)b->am_nb[w];
+    if (n_b) *n_b = (int32_t)n;
+    if (F) for (int j = 0; j < 2; j++) memcpy(F + j * n, r + LBD_REC_F + j * SWF_LAMBDA_NMAX, n * sizeof(double));
+    if (s) memcpy(s, r + LBD_REC_S, 2 * sizeof(double));
+    if (ratio) memcpy(ratio, r + LBD_REC_RATIO, 2 * sizeof(double));
+    if (fixed) *fixed = (int32_t)r[LBD_REC_INFO + 1];
+    if (Qb) memcpy(Qb, r + LBD_REC_QB, n * n * sizeof(double));
+    if (bf) memcpy(bf, r + LBD_REC_BF, n * sizeof(double));
+    if (info) *info = (int32_t)r[LBD_REC_INFO];
     return SWF_OK;
 }
 

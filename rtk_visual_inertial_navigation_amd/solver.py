@@ -55,6 +55,7 @@ EXPORTED = [
     "swf_composite_set_mid_links", "swf_composite_add_mid_prior", "swf_set_imu_gnss_mid_link", "swf_composite_set_root",
     "swf_batch_create_on", "swf_batch_create_sharded", "swf_solve_batches", "swf_batch_device", "swf_default_options", "swf_shard_partition",
     "swf_prior_reset_linearization_point",
+    "swf_lambda_batch", "swf_batch_ambiguity_search", "swf_batch_get_ambiguity_fix",
 ]
 
 
@@ -207,6 +208,28 @@ class BatchSolver:
                  "swf_batch_get_tail_covariance")
             return dict(A=A, Qy=Q, n=k)
         return [one(i) for i in range(self.n)] if w is None else one(w)
+
+    def ambiguity_search(self, pairs_per_window, ratio_threshold=2.0):
+        """LambdaSearch's numeric core for every window (R/swf/swf_lambda.cpp:82-365), on the device after tail_covariance():
+        pairs_per_window[w] = [(tail coordinate of an ambiguity, tail coordinate of its reference ambiguity), ...].  Returns one
+        dict per window: F [2][n_b], s [2], ratio [2], fixed, Qb = D Qy D^T, bf = D y, n_b, info (SWF_LAMBDA_*)."""
+        first = np.zeros(self.n + 1, np.int32)
+        for w, pw in enumerate(pairs_per_window):
+            first[w + 1] = first[w] + len(pw)
+        flat = np.ascontiguousarray(np.array([q for pw in pairs_per_window for q in pw], np.int32).reshape(-1, 2)) if first[-1] else np.zeros((1, 2), np.int32)
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_batch_ambiguity_search(self._h, first.ctypes.data_as(pi), flat.ctypes.data_as(pi), C.c_double(ratio_threshold)),
+             "swf_batch_ambiguity_search")
+        out = []
+        for w in range(self.n):
+            k = len(pairs_per_window[w])
+            F, sv, r, Qb, bf = np.zeros((2, k)), np.zeros(2), np.zeros(2), np.zeros((k, k)), np.zeros(k)
+            fx, nb, info = C.c_int32(), C.c_int32(), C.c_int32()
+            _chk(lib().swf_batch_get_ambiguity_fix(self._h, C.c_int32(w), F.ctypes.data_as(_pd), sv.ctypes.data_as(_pd), r.ctypes.data_as(_pd),
+                                                   C.byref(fx), Qb.ctypes.data_as(_pd), bf.ctypes.data_as(_pd), C.byref(nb), C.byref(info)),
+                 "swf_batch_get_ambiguity_fix")
+            out.append(dict(F=F, s=sv, ratio=r, fixed=bool(fx.value), Qb=Qb, bf=bf, n_b=nb.value, info=info.value))
+        return out
 
     def enable_timing(self, mask=1):
         """mask: bit k brackets kernel K_NAMES[k] with a HIP event pair per launch (bit 0 = whole solve);
@@ -704,6 +727,29 @@ def triangulate_batch(Ps, Rs, tic, ric, pbg, start_frame, pt0, pt1, init_depth=5
                                      C.c_int32(n), C.c_double(init_depth), depth.ctypes.data_as(_pd), world.ctypes.data_as(_pd),
                                      C.c_int32(0), None), "triangulate_batch")
     return depth, world
+
+
+LAMBDA_OK, LAMBDA_NOT_PD, LAMBDA_LOOP_LIMIT, LAMBDA_NO_INPUT = 0, 1, 2, 3
+
+
+def lambda_batch(a_list, Q_list, m=2):
+    """RTKLIB's lambda() (R/gnss/src/lambda.cpp:58-235) for a batch of problems on the device (swf_lambda_batch): float solutions
+    a_list[p] [n_p] with covariances Q_list[p] [n_p][n_p], n_p <= 64.  Returns one (F [m][n_p], s [m], info) per problem."""
+    P = len(a_list)
+    ns = np.array([np.asarray(a).size for a in a_list], np.int32)
+    ld = max(1, int(ns.max()) if P else 1)
+    A = np.zeros((max(P, 1), ld))
+    Q = np.zeros((max(P, 1), ld, ld))
+    for p in range(P):
+        k = ns[p]
+        A[p, :k] = np.asarray(a_list[p], np.float64).ravel()
+        Q[p, :k, :k] = np.asarray(Q_list[p], np.float64).T          # column-major
+    F, s, info = np.zeros((max(P, 1), m, ld)), np.zeros((max(P, 1), m)), np.zeros(max(P, 1), np.int32)
+    pi = C.POINTER(C.c_int32)
+    _chk(lib().swf_lambda_batch(C.c_int32(P), C.c_int32(ld), ns.ctypes.data_as(pi), A.ctypes.data_as(_pd), Q.ctypes.data_as(_pd),
+                                C.c_int32(m), F.ctypes.data_as(_pd), s.ctypes.data_as(_pd), info.ctypes.data_as(pi), C.c_int32(0), None),
+         "swf_lambda_batch")
+    return [(F[p, :, :ns[p]].copy(), s[p].copy(), int(info[p])) for p in range(P)]
 
 
 def problem_from_window(w):
