@@ -137,7 +137,7 @@ struct DevBatch {
     // a dozen block values in block order instead of reading 16 B per observation; per-observation costs are not stored any more.
     double* p_cpart; double* p_apart;
     // two-level per-frame sums: blocks of <= 256 observations of one window
-    int n_fsb; const int* fsb_win; const int* fsb_obs0; const int* fsb_perm; const int* fsb_foff; const int* fsb_foff0; const int* fsb_out0;
+    int n_fsb; const int* fsb_rec; const int* fsb_perm; const int* fsb_foff;   // fsb_rec: 8 ints per block (ProjBlk, swf_kernels.h)
     double* fs_part;
     double* jsc;                 // [n_loc_total] Jacobi scaling of the solve's first linearisation, (1 + sqrt(diag))^2 (Solver::Options::jacobi_scaling)
     // landmarks

@@ -1046,7 +1046,17 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
     PUT(fr_obs0, B.fr_obs0); PUT(fr_obs, B.fr_obs); PUT(fr_red, B.fr_red);
     D.n_fsb = (int)B.fsb_win.size();
     B.fsb_obs0.push_back(D.n_proj); B.fsb_perm.resize((size_t)D.n_proj + 1, 0);
-    PUT(fsb_win, B.fsb_win); PUT(fsb_obs0, B.fsb_obs0); PUT(fsb_perm, B.fsb_perm); PUT(fsb_foff, B.fsb_foff); PUT(fsb_foff0, B.fsb_foff0); PUT(fsb_out0, B.fsb_out0);
+    {
+        // one 32-byte record per frame-sum block (layout: ProjBlk, swf_kernels.h): everything the block's evaluation needs to address its loads comes with ONE load
+        std::vector<int> rec((size_t)8 * std::max(D.n_fsb, 1), 0);
+        for (int k = 0; k < D.n_fsb; k++) {
+            int* r = rec.data() + (size_t)8 * k;
+            r[0] = B.fsb_win[(size_t)k]; r[1] = B.fsb_obs0[(size_t)k]; r[2] = B.fsb_obs0[(size_t)k + 1] - B.fsb_obs0[(size_t)k];
+            r[3] = B.fsb_foff0[(size_t)k]; r[4] = B.fsb_out0[(size_t)k]; r[5] = B.win[(size_t)r[0]].nF;
+        }
+        PUT(fsb_rec, rec);
+    }
+    PUT(fsb_perm, B.fsb_perm); PUT(fsb_foff, B.fsb_foff);
     rc |= P.zeros((size_t)B.fs_tot * FS_VAL, &D.fs_part);
     rc |= P.zeros((size_t)std::max<long long>(B.n_loc, 1), &D.jsc);
     D.n_gf = (int)B.gf.size();
@@ -2361,6 +2371,14 @@ extern "C" int swf_debug_dog_stamps(unsigned long long* out) {
 extern "C" int swf_debug_clq_stamps(unsigned long long* out) {
     if (hipDeviceSynchronize() != hipSuccess) return SWF_E_NODEVICE;
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_clq_stamps), 16 * sizeof(unsigned long long)) != hipSuccess) return SWF_E_NODEVICE;
+    return SWF_OK;
+}
+#endif
+
+#ifdef SWF_PROFILE_EVAL
+extern "C" int swf_debug_eval_stamps(unsigned long long* out) {
+    if (hipDeviceSynchronize() != hipSuccess) return SWF_E_NODEVICE;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_eval_stamps), 16 * sizeof(unsigned long long)) != hipSuccess) return SWF_E_NODEVICE;
     return SWF_OK;
 }
 #endif

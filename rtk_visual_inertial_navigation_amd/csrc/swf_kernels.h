@@ -62,28 +62,67 @@ template <bool JAC> __device__ __forceinline__ const double* eval_src(const DevB
 // block is constant) — for the per-frame sums of the fused evaluation kernel, and, with STORE = false (nothing written), for the
 // back-substitution pass, which re-derives an observation's Jacobian from its 56 B of inputs instead of re-reading 144 B
 // the arithmetic of one observation from its inputs in registers (P pose, E extrinsic, X landmark, (u0, u1) image point; jp / jl: the pose /
-// the landmark is variable) — d_eval_proj_at below loads them one dependent level after another; the back-substitution pass fetches
-// them together with everything else it needs
+// the landmark is variable) — ProjBlk below and the back-substitution pass fetch them by dependency level, together with everything
+// else they need
 // returns the observation's cost (0.5 rho(|r|^2)); the caller's block adds its observations' costs into one partial sum
 template <bool JAC, bool STORE>
 __device__ __forceinline__ double proj_core(const DevBatch& B, int i, const WinRec& W, const double* P, const double* E, const double* X,
                                           double u0, double u1, bool jp, bool jl, double* keep);
-template <bool JAC, bool STORE = true>
-__device__ __forceinline__ double d_eval_proj_at(const DevBatch& B, int i, double* keep) {
-    int w = B.p_win[i];
-    const WinState& s = B.ws[w];
-    if (!eval_gate<JAC>(B, s)) return 0.0;
-    const WinRec& W = B.win[w];
-    const double* xs = eval_src<JAC>(B);
-    const double* pose = xs + B.p_xpose[i];
-    const double* ex = xs + B.p_xex[i];
-    const double* lm = xs + B.p_xlm[i];
-    double P[7], E[7], X[3];
+#ifdef SWF_PROFILE_EVAL
+// phase stamps of the projection segment's block 0, thread 0 (-DSWF_PROFILE_EVAL, swf_debug_eval_stamps): cycles spent up to
+// 0 the block record, 1 the indices and window constants, 2 the state values, 3 proj_core, 4 the block's cost, 5 the frame sums.
+// The wait in front of a stamp makes the level's loads land before the clock is read (the product build waits where a value is used).
+__device__ unsigned long long g_eval_stamps[16];
+#define EST(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); g_eval_stamps[i] = t_ - te_; te_ = t_; } } while (0)
+#else
+#define EST(i)
+#endif
+// Everything one lane of a frame-sum block's evaluation reads, fetched by dependency level, each level issued as a whole (the chain
+// it replaces walked block -> window flags -> ranges -> observation's window -> flags again -> indices -> state, about seven
+// exposed round trips before the first flop; d_backsub_lm, swf_kernels2.h, got the same treatment in round 4):
+//   (1) the block record, one 32-byte load: 8 ints { window, first observation, observations, first entry in fsb_foff,
+//       first row in fs_part, observing frames of the window, 0, 0 }, host-built next to the fsb_* tables;
+//   (2) unconditionally, with the lane's observation clamped into the block: the window's flags and constants, the observation's
+//       indices and image point, (JAC) its rank in the frame-sorted order;
+//   (3) the 17 state values at eval_src (which depends on the launch only, not on the window).
+// The gate is the block's window's: a frame-sum block holds observations of ONE window.
+template <bool JAC>
+struct ProjBlk {
+    int cnt, foff0, out0, nF, rk, lp, ll, fo;  // fo (JAC): entry tid of the block's frame offsets (the staging tile's tail holds at most 170 of them)
+    bool gate;
+    WinRec W;                                  // pbg, proj_sqrt_info, proj_loss_a only: what proj_core reads
+    double P[7], E[7], X[3], u0, u1;
+    int o;
+#ifdef SWF_PROFILE_EVAL
+    unsigned long long te_;
+#endif
+    __device__ __forceinline__ void load(const DevBatch& B, int blk) {
+#ifdef SWF_PROFILE_EVAL
+        te_ = __builtin_amdgcn_s_memtime();
+#endif
+        const int4 r0 = ((const int4*)B.fsb_rec)[2 * blk], r1 = ((const int4*)B.fsb_rec)[2 * blk + 1];
+        const int w = r0.x, tid = threadIdx.x;
+        cnt = r0.z; foff0 = r0.w; out0 = r1.x; nF = r1.y;
+        o = tid < cnt ? r0.y + tid : r0.y;
+        if (JAC) EST(0);                          // (the cost-only pass shares block 0: it leaves the stamps alone)
+        const WinState& s = B.ws[w];
+        const WinRec& Wg = B.win[w];
+        const int need = s.need_lin, cand = s.eval_cand;
+        W.pbg[0] = Wg.pbg[0]; W.pbg[1] = Wg.pbg[1]; W.pbg[2] = Wg.pbg[2]; W.proj_sqrt_info = Wg.proj_sqrt_info; W.proj_loss_a = Wg.proj_loss_a;
+        const int xpo = B.p_xpose[o], xex = B.p_xex[o], xlm = B.p_xlm[o];
+        lp = JAC ? B.p_lpose[o] : -1; ll = JAC ? B.p_llm[o] : -1; rk = JAC ? B.fsb_perm[o] : 0;
+        u0 = B.p_uv[2 * o]; u1 = B.p_uv[2 * o + 1];
+        fo = JAC ? B.fsb_foff[foff0 + (tid <= nF ? tid : 0)] : 0;
+        if (JAC) EST(1);
+        const double* xs = eval_src<JAC>(B);
 #pragma unroll
-    for (int k = 0; k < 7; k++) { P[k] = pose[k]; E[k] = ex[k]; }
-    X[0] = lm[0]; X[1] = lm[1]; X[2] = lm[2];
-    return proj_core<JAC, STORE>(B, i, W, P, E, X, B.p_uv[2 * i], B.p_uv[2 * i + 1], JAC && B.p_lpose[i] >= 0, JAC && B.p_llm[i] >= 0, keep);
-}
+        for (int k = 0; k < 7; k++) { P[k] = xs[xpo + k]; E[k] = xs[xex + k]; }
+#pragma unroll
+        for (int k = 0; k < 3; k++) X[k] = xs[xlm + k];
+        if (JAC) EST(2);
+        gate = B.spec == 2 ? true : (JAC && !B.spec) ? need != 0 : cand != 0;       // eval_gate<JAC>, from the values fetched above
+    }
+};
 template <bool JAC, bool STORE>
 __device__ __forceinline__ double proj_core(const DevBatch& B, int i, const WinRec& W, const double* P, const double* E, const double* X,
                                           double u0, double u1, bool jp, bool jl, double* keep) {
@@ -147,15 +186,30 @@ __device__ __forceinline__ double proj_core(const DevBatch& B, int i, const WinR
     return cost;
 }
 
+// proj_core on what ProjBlk fetched.  A function of its own, taking the values in the order the loads used to stand in (pose and extrinsic
+// interleaved, landmark, image point, flags; the window constants where proj_core reads them), and on purpose: the compiler settles
+// the operand order of proj_core's commutative floating-point operations while it optimises this function by itself, from the order
+// of these reads, and a * b + c * d contracts to fma(a, b, c * d) or fma(c, d, a * b) by that order.  Handing proj_core the fields
+// directly rounds its rotation products the other way (measured: states differ in the 8th digit after 8 iterations).
+template <bool JAC>
+__device__ __forceinline__ double d_eval_proj_at(const DevBatch& B, const ProjBlk<JAC>& Q, double* keep) {
+    double P[7], E[7], X[3];
+#pragma unroll
+    for (int k = 0; k < 7; k++) { P[k] = Q.P[k]; E[k] = Q.E[k]; }
+    X[0] = Q.X[0]; X[1] = Q.X[1]; X[2] = Q.X[2];
+    return proj_core<JAC, true>(B, Q.o, Q.W, P, E, X, Q.u0, Q.u1, JAC && Q.lp >= 0, JAC && Q.ll >= 0, keep);
+}
+
 // cost-only evaluation of one frame-sum block's observations at the candidate (k_post_dogleg): the block's cost in p_cpart, formed
 // exactly as the Jacobian evaluation of the same block forms it (d_eval_proj_fs: thread t <-> observation t of the block, block_sum)
 __device__ __forceinline__ void d_eval_proj_cost(const DevBatch& B, int blk) {
     __shared__ double csum[16];
-    const int w = B.fsb_win[blk];
-    if (!eval_gate<false>(B, B.ws[w])) return;               // uniform per block (a block holds observations of one window)
-    const int o_beg = B.fsb_obs0[blk], cnt = B.fsb_obs0[blk + 1] - o_beg, tid = threadIdx.x;
+    ProjBlk<false> Q;
+    Q.load(B, blk);
+    if (!Q.gate) return;                                     // uniform per block (a block holds observations of one window)
+    const int tid = threadIdx.x;
     double c = 0.0;
-    if (tid < cnt) c = d_eval_proj_at<false>(B, o_beg + tid, nullptr);
+    if (tid < Q.cnt) c = d_eval_proj_at<false>(B, Q, nullptr);
     c = block_sum(c, csum);
     if (tid == 0) B.p_cpart[blk] = c;
 }
@@ -1426,23 +1480,27 @@ __global__ void __launch_bounds__(CB_NT) k_clique_big2(DevBatch B, DevOpt O) {
 // The same, fused into the Jacobian evaluation (k_eval_ps<true>, one workgroup per frame-sum block): thread t evaluates observation t of
 // the block and the 27 products never leave the chip — Jp and r are not read back (112 B per observation and one launch less).
 __device__ __forceinline__ void d_eval_proj_fs(const DevBatch& B, int blk, double (*V)[FS_HALF], int* foff) {
-    int w = B.fsb_win[blk];
-    if (!eval_gate<true>(B, B.ws[w])) return;                // uniform per block (a block holds observations of one window)
-    const WinRec& W = B.win[w];
-    int o_beg = B.fsb_obs0[blk], cnt = B.fsb_obs0[blk + 1] - o_beg, tid = threadIdx.x;
-    int nF = W.nF;
-    for (int e = tid; e <= nF; e += FS_BLK) foff[e] = B.fsb_foff[B.fsb_foff0[blk] + e];
+    ProjBlk<true> Q;
+    Q.load(B, blk);
+#ifdef SWF_PROFILE_EVAL
+    unsigned long long& te_ = Q.te_;
+#endif
+    const int tid = threadIdx.x, cnt = Q.cnt, nF = Q.nF, rk = Q.rk;
+    if (!Q.gate) return;                                     // uniform per block (a block holds observations of one window)
+    if (tid <= nF) foff[tid] = Q.fo;
+    for (int e = tid + FS_BLK; e <= nF; e += FS_BLK) foff[e] = B.fsb_foff[Q.foff0 + e];
     double keep[20];
 #pragma unroll
     for (int k = 0; k < 20; k++) keep[k] = 0.0;
-    int rk = 0;
     double cost = 0.0;
-    if (tid < cnt) { rk = B.fsb_perm[o_beg + tid]; cost = d_eval_proj_at<true>(B, o_beg + tid, keep); }
+    if (tid < cnt) cost = d_eval_proj_at<true>(B, Q, keep);
+    EST(3);
     {   // the block's cost (what the per-window control kernels add up instead of per-observation costs)
         __shared__ double csum[16];
         cost = block_sum(cost, csum);
         if (tid == 0) B.p_cpart[blk] = cost;
     }
+    EST(4);
     double val[FS_VAL];
     {
         const double* a = keep; const double* b = keep + 6;
@@ -1454,7 +1512,7 @@ __device__ __forceinline__ void d_eval_proj_fs(const DevBatch& B, int blk, doubl
 #pragma unroll
         for (int i = 0; i < 6; i++) val[21 + i] = a[i] * keep[12] + b[i] * keep[13];
     }
-    double* out = B.fs_part + (size_t)B.fsb_out0[blk] * FS_VAL;
+    double* out = B.fs_part + (size_t)Q.out0 * FS_VAL;
 #pragma unroll
     for (int half = 0; half < 2; half++) {
         const int v0 = half * FS_HALF, nv = half == 0 ? FS_HALF : FS_VAL - FS_HALF;
@@ -1476,6 +1534,7 @@ __device__ __forceinline__ void d_eval_proj_fs(const DevBatch& B, int blk, doubl
             out[f * FS_VAL + v0 + v] = acc;
         }
     }
+    EST(5);
 }
 
 // =========================================================================================

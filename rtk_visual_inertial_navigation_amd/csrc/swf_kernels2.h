@@ -932,8 +932,10 @@ struct Segs { int e[8]; };     // exclusive end block of segment k (cumulative)
 // behind this one — the two evaluations are independent, and on the latency path a launch costs its whole dependent-load chain
 // (one window: 7.6 + 11.8 us as two kernels).  Large batches keep k_eval_imu apart: its LDS and registers would cost the HBM-bound
 // segments their occupancy.  Same device functions, same results.
+// (the batch instantiation is held at 5 waves per SIMD, 96 registers: left alone the compiler spends 108 on keeping the projection
+// segment's loads in flight and the HBM-bound segment loses a fifth of its resident blocks)
 template <bool JAC, bool FS = false, bool IMU = false>
-__global__ void __launch_bounds__(256) k_eval_ps(DevBatch B, Segs S) {
+__global__ void __launch_bounds__(256, (FS && !IMU) ? 5 : 1) k_eval_ps(DevBatch B, Segs S) {
     // one LDS buffer for whichever segment the block runs: the prior's staging vectors, or the frame sums' staging tile (+ its frame offsets)
     constexpr int SM_PRIOR = 2 * PRIOR_LDS_DIM + 16, SM_FS = FS ? FS_BLK * FS_HALF + 168 / 2 + 1 : 1;
     __shared__ double sm[SM_PRIOR > SM_FS ? SM_PRIOR : SM_FS];
