@@ -535,4 +535,17 @@ inline int lambda(int n, int m, const double* a, const double* Q, double* F, dou
     return 0;
 }
 
+// SWFOptimization::OutliersRejection (R/swf/swf_image.cpp:263-308) together with the depth-sign test of Double2Vector
+// (R/swf/swf.cpp:214-229), on the device, after Solve: `failed` receives the parameter blocks (landmarks / inverse depths) whose
+// mean reprojection error times FOCAL_LENGTH / FEATUREWEIGHTINVERSE exceeds `threshold` (the reference: 2) or whose depth is
+// negative — the blocks ImagePostprocess hands to FeatureManager::removeFailures.  False when the check could not run.
+inline bool OutliersRejection(Problem& p, double threshold, std::vector<double*>& failed) {
+    failed.clear();
+    if (swf_problem_check_features(p.handle(), threshold) != SWF_OK) return false;
+    int32_t n = 0;
+    if (swf_problem_rejected_features(p.handle(), nullptr, 0, &n) != SWF_OK) return false;
+    failed.resize((size_t)n);
+    return n == 0 || swf_problem_rejected_features(p.handle(), failed.data(), n, &n) == SWF_OK;
+}
+
 }  // namespace swf_ceres

@@ -51,6 +51,9 @@ enum {
  * 107: no layout change; the LAMBDA integer ambiguity search on the device: swf_lambda_batch (stand-alone, RTKLIB's lambda() for a batch
  * of problems) and swf_batch_ambiguity_search / swf_batch_get_ambiguity_fix (LambdaSearch's numeric core after
  * swf_batch_tail_covariance, ratio test included).
+ * 108: no layout change; the post-solve feature check on the device: swf_batch_check_features / swf_batch_get_feature_check
+ * (OutliersRejection's mean reprojection error and Double2Vector's depth sign per feature, the rejected list compacted on the
+ * device), swf_problem_check_features / swf_problem_get_feature_check / swf_problem_rejected_features by parameter-block key.
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);
@@ -206,6 +209,37 @@ int swf_batch_get_tail_covariance(swf_batch* b, int32_t w, double* A, double* Qy
 int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_first, const int32_t* pairs, double ratio_threshold);
 int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, double* s, double* ratio, int32_t* fixed,
                                 double* Qb, double* bf, int32_t* n_b, int32_t* info);
+
+/* Post-solve feature check: what the reference does to every feature after every window solve — the depth-sign test of
+ * SWFOptimization::Double2Vector (R/swf/swf.cpp:214-229) and the mean reprojection error of OutliersRejection
+ * (R/swf/swf_image.cpp:255-308) — for every window, on the device, without moving the state to the host.  Read-only: it reads the
+ * state swf_batch_download_state would return at that moment (after a solve the accepted point; after swf_batch_upload_state /
+ * swf_batch_reset_state the uploaded one) and writes nothing a solve, an export, a marginalisation or an ambiguity search reads.
+ * Features of window w, in this order: its n_lm world-point landmarks in pool order, then its inverse-depth features = the distinct
+ * scalar-pool blocks idp_idx[][4] names, ascending.  Per feature, with P_j = p_j - R_j pbg and R from the normalised quaternion:
+ *   world point X       for each of its projection factors k (frame j, extrinsic e, image point uv) in the caller's factor order:
+ *                       pc = R_e^T (R_j^T (X - P_j) - t_e), err_k = |pc.xy / pc.z - uv|; mean_err = (sum err_k) / n_obs, summed left
+ *                       to right; depth = pc.z of its first factor.
+ *   inverse depth lam   anchor pose i and anchor point pts_i from its factors: X = R_i (R_ex (pts_i / lam) + t_ex - pbg) + p_i, then
+ *                       the same error for every factor with its pts_j (kinds 1 / 2 in the second camera; kind 2 in the anchor frame),
+ *                       preceded by one term for the anchor's own observation (X back in the anchor's first camera against pts_i:
+ *                       the reference's loop starts at start_frame); n_obs = factors + 1; depth = 1 / lam.  A lam that only kind-2
+ *                       factors name has no pose: it is evaluated in the anchor's body frame.  Factors of one lam that disagree on
+ *                       (pose_i, pts_i): SWF_E_INVALID from swf_batch_check_features.
+ *   flags               SWF_FEAT_OUTLIER iff mean_err * proj_sqrt_info > max_mean_error (the reference: 2, strict);
+ *                       SWF_FEAT_NEG_DEPTH iff depth < 0 (world point) / lam < 0 (inverse depth); SWF_FEAT_UNOBSERVED for a landmark
+ *                       no projection factor names (mean_err = depth = 0, never rejected).  A NaN mean sets neither bit.
+ * Constant landmarks, landmarks outside elimination group 0 and factors with a variable extrinsic are covered like any other.
+ * swf_batch_check_features is asynchronous on the batch stream (the first call builds the check's observation table).  The getter
+ * synchronises; its first call after a check copies every window's results to the host once, later calls read that copy.  Arrays
+ * are [n_feat]; rejected [<= n_feat] = the indices of the features with OUTLIER | NEG_DEPTH, ascending (compacted on the device).
+ * Any pointer may be NULL.  Results are invalidated by the next swf_batch_solve / _upload_state / _reset_state (SWF_E_STATE, as is
+ * a getter before any check); w out of range, max_mean_error not finite or < 0: SWF_E_INVALID.  Removing the rejected blocks
+ * (FeatureManager::removeFailures) stays with the caller. */
+enum { SWF_FEAT_OUTLIER = 1, SWF_FEAT_NEG_DEPTH = 2, SWF_FEAT_UNOBSERVED = 4 };
+int swf_batch_check_features(swf_batch* b, double max_mean_error);
+int swf_batch_get_feature_check(swf_batch* b, int32_t w, double* mean_err, double* depth, int32_t* n_obs, uint8_t* flags,
+                                int32_t* rejected, int32_t* n_rejected, int32_t* n_feat);
 
 /* Timing of the last swf_batch_solve, measured with HIP events recorded on the batch stream
  * around individual kernel launches (valid after swf_batch_sync).  `mask` selects which
@@ -517,6 +551,13 @@ int swf_problem_marginalize(swf_problem* p, double eps, int32_t form, const doub
  * the problem and valid until the next call / solve. */
 int swf_problem_tail_covariance(swf_problem* p, const double** A, const double** Qy, int32_t* n);
 int swf_get_reduced(swf_problem* p, const double** S, const double** rhs, const double** L, int32_t* hs_row);
+/* The feature check (see swf_batch_check_features) on the problem's cached batch, valid after swf_problem_solve (SWF_E_STATE
+ * otherwise): features are the size-3 blocks and the inverse depths of swf_add_projection_inverse_depth, addressed by key
+ * (SWF_E_NOTFOUND for a key that is no feature of the last solve).  swf_problem_rejected_features writes up to cap keys of the
+ * features with OUTLIER | NEG_DEPTH, in feature order, and their full count to *n.  Any out pointer may be NULL. */
+int swf_problem_check_features(swf_problem* p, double max_mean_error);
+int swf_problem_get_feature_check(swf_problem* p, const double* key, double* mean_err, double* depth, int32_t* n_obs, int32_t* flags);
+int swf_problem_rejected_features(swf_problem* p, double** keys, int32_t cap, int32_t* n);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
 #include "swf_kernels3.h"
 #include "swf_kernels4.h"
 #include "swf_lambda.h"
+#include "swf_features.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -28,7 +29,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 extern "C" const char* swf_last_error(void) { return g_err.c_str(); }
 void swf_internal_set_error(const std::string& m) { g_err = m; }
-extern "C" int swf_version(void) { return 107; }
+extern "C" int swf_version(void) { return 108; }
 extern "C" int swf_abi_sizes(int32_t out[5]) {
     if (!out) return fail(SWF_E_INVALID, "swf_abi_sizes: null");
     out[0] = (int32_t)sizeof(swf_options); out[1] = (int32_t)sizeof(swf_summary); out[2] = (int32_t)sizeof(swf_timing);
@@ -202,6 +203,7 @@ struct HostWin {       // what the host keeps per window for state transfer / ex
     std::vector<int> p_orig;                            // device observation (proj0 + q) -> the caller's projection factor index
     int n_proj_all = 0;                                 // the caller's projection factors, fast path + generic path (GF_PROJX)
     std::vector<int> tail_x;                            // per tail coordinate: its state index if its block has size 1, else -1
+    FeatWinSrc feat;                                    // the window's visual factors as the caller gave them (swf_batch_check_features builds its table from them)
 };
 
 struct swf_batch {
@@ -235,6 +237,10 @@ struct swf_batch {
     bool am_valid = false, am_host = false; std::vector<double> h_am;
     std::vector<int> am_nb;                             // pairs per window of the last search
     std::vector<int> am_h_first; std::vector<int4> am_h_pairs;      // host staging of the pair upload (outlives the asynchronous copy)
+    // post-solve feature check (swf_features.h): the observation table and the output buffer are allocated at the first
+    // swf_batch_check_features; fc_out = mean_err | depth | n_obs | rejected | n_rejected | flags, mirrored to the host by the first getter
+    bool fc_built = false, fc_valid = false, fc_host = false; FeatArgs fc{}; char* fc_out = nullptr; size_t fc_bytes = 0; int fc_nfeat = 0;
+    std::vector<int> fc_feat0; std::vector<char> h_fc;
     // latency path (small batches): an auxiliary stream runs the IMU / clique branch of a linearisation next to the
     // projection / landmark branch; three reusable events carry the dependencies
     hipStream_t aux = nullptr; hipEvent_t ev_fork[3] = { nullptr, nullptr, nullptr };
@@ -370,6 +376,17 @@ int build_window(Build& B, const swf_flat_window* w, int wi, HostWin& hw) {
         if (loc[bidP(ex)] >= 0 || (loc[bidL(l)] >= 0 && !is_e(bidL(l)))) lm_generic[l] = 1;
     }
     hw.n_proj_all = w->n_proj;
+    {
+        FeatWinSrc& fs = hw.feat;
+        fs.x_base = R.x_base; fs.n_pose = nP; fs.n_sb = nS; fs.n_lm = nL; fs.n_sc = nC;
+        if (w->n_proj > 0) { fs.proj_idx.assign(w->proj_idx, w->proj_idx + (size_t)3 * w->n_proj); fs.proj_uv.assign(w->proj_uv, w->proj_uv + (size_t)2 * w->n_proj); }
+        if (w->n_idp > 0) {
+            fs.idp_kind.assign(w->idp_kind, w->idp_kind + w->n_idp); fs.idp_idx.assign(w->idp_idx, w->idp_idx + (size_t)5 * w->n_idp);
+            fs.idp_pts.assign(w->idp_pts, w->idp_pts + (size_t)6 * w->n_idp);
+        }
+        for (int k = 0; k < 3; k++) fs.pbg[k] = w->pbg[k];
+        fs.sqrt_info = w->proj_sqrt_info;
+    }
     // ---- projection observations of the fast path sorted by (landmark, pose)
     std::vector<int> ord;
     for (int i = 0; i < w->n_proj; i++) if (!lm_generic[w->proj_idx[i * 3 + 2]]) ord.push_back(i);
@@ -1427,12 +1444,14 @@ extern "C" int swf_batch_upload_state(swf_batch* b) {
         HIPCHK(hipMemsetAsync(b->CA.history, 0, (size_t)b->n_comp * sizeof(int), b->stream));
     }
     HIPCHK(hipStreamSynchronize(b->stream));     // staging buffers have stack lifetime
+    b->fc_valid = false;
     return SWF_OK;
 }
 
 extern "C" int swf_batch_reset_state(swf_batch* b) {
     DeviceGuard dg_(b ? b->device : -1);
     if (!b) return fail(SWF_E_INVALID, "null batch");
+    b->fc_valid = false;
     int n = b->D.n_x;
     hipLaunchKernelGGL(k_copy, dim3((n + 255) / 256), dim3(256), 0, b->stream, b->D.x, (const double*)b->D.x0, n);
     HIPCHK(hipGetLastError());
@@ -1831,7 +1850,7 @@ extern "C" int swf_batch_solve(swf_batch* b, const swf_options* opt) {
     b->last.lm_schur_flops = b->lm_schur_flops; b->last.n_obs = b->D.n_proj;
     b->last.lm_schur_flops_sym = b->lm_schur_flops_sym; b->last.lm_schur_mfma = b->lm_schur_mfma;
     b->last.n_linearizations = nlin;
-    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false; b->am_valid = false;      // consumer outputs belong to the previous solve
+    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false; b->am_valid = false; b->fc_valid = false;      // consumer outputs belong to the previous solve
     return SWF_OK;
 }
 
@@ -2200,6 +2219,69 @@ extern "C" int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, d
     if (Qb) memcpy(Qb, r + LBD_REC_QB, n * n * sizeof(double));
     if (bf) memcpy(bf, r + LBD_REC_BF, n * sizeof(double));
     if (info) *info = (int32_t)r[LBD_REC_INFO];
+    return SWF_OK;
+}
+
+// post-solve feature check (OutliersRejection + the depth sign of Double2Vector): k_feature_err, k_feature_compact
+extern "C" int swf_batch_check_features(swf_batch* b, double max_mean_error) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b) return fail(SWF_E_INVALID, "swf_batch_check_features: null batch");
+    if (!std::isfinite(max_mean_error) || max_mean_error < 0) return fail(SWF_E_INVALID, "swf_batch_check_features: max_mean_error must be finite and >= 0");
+    const int nw = (int)b->win.size();
+    if (!b->fc_built) {          // symbolic phase of the check, once per batch
+        std::vector<FeatWinSrc> src(nw);
+        for (int w = 0; w < nw; w++) src[w] = b->hw[w].feat;
+        FeatTables T;
+        const int rc0 = swf_internal_feature_tables(src, T);
+        if (rc0) return rc0;
+        const size_t nf = T.f_obs0.size() - 1;
+        FeatArgs& A = b->fc;
+        int rc = 0;
+        rc |= b->pool.put(T.o_a, &A.o_a); rc |= b->pool.put(T.o_b, &A.o_b); rc |= b->pool.put(T.o_uv, &A.o_uv);
+        rc |= b->pool.put(T.f_obs0, &A.f_obs0); rc |= b->pool.put(T.f_pi, &A.f_pi); rc |= b->pool.put(T.blk, &A.blk);
+        rc |= b->pool.put(T.w_feat0, &A.w_feat0); rc |= b->pool.put(T.w_cst, &A.w_cst);
+        // one output buffer, 8-byte fields first: mean_err [nf] | depth [nf] | n_obs [nf] | rejected [nf] | n_rejected [nw] | flags [nf]
+        b->fc_bytes = nf * (2 * sizeof(double) + 2 * sizeof(int) + 1) + (size_t)nw * sizeof(int);
+        rc |= b->pool.zeros(b->fc_bytes, &b->fc_out);
+        if (rc) return fail(SWF_E_NODEVICE, "device allocation failed");
+        HIPCHK(hipStreamSynchronize(nullptr));      // the pool initialises late allocations on the default stream; the kernels run on the batch's
+        A.mean_err = (double*)b->fc_out; A.depth = A.mean_err + nf; A.n_obs = (int*)(A.depth + nf); A.rejected = A.n_obs + nf;
+        A.n_rejected = A.rejected + nf; A.flags = (unsigned char*)(A.n_rejected + nw);
+        A.n_blk = (int)T.blk.size(); A.n_win = nw;
+        b->fc_nfeat = (int)nf; b->fc_feat0 = T.w_feat0;
+        for (int w = 0; w < nw; w++) b->hw[w].feat = FeatWinSrc{};          // the table has them now
+        b->fc_built = true;
+    }
+    b->fc.x = b->D.x; b->fc.thr = max_mean_error;
+    b->fc_valid = false;
+    const int rc = swf_internal_feature_launch(b->fc, b->stream);
+    if (rc) return rc;
+    b->fc_valid = true; b->fc_host = false;
+    return SWF_OK;
+}
+
+extern "C" int swf_batch_get_feature_check(swf_batch* b, int32_t w, double* mean_err, double* depth, int32_t* n_obs, uint8_t* flags,
+                                           int32_t* rejected, int32_t* n_rejected, int32_t* n_feat) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b || w < 0 || w >= (int)b->win.size()) return fail(SWF_E_INVALID, "bad window index");
+    if (!b->fc_valid) return fail(SWF_E_STATE, "swf_batch_get_feature_check before swf_batch_check_features (or after a new solve / state upload)");
+    if (!b->fc_host) {           // the first getter after a check copies every window's results in one transfer
+        b->h_fc.resize(b->fc_bytes);
+        HIPCHK(hipMemcpyAsync(b->h_fc.data(), b->fc_out, b->fc_bytes, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        b->fc_host = true;
+    }
+    const size_t nf = (size_t)b->fc_nfeat, nw = b->win.size(), f0 = (size_t)b->fc_feat0[w], n = (size_t)b->fc_feat0[w + 1] - f0;
+    const double* h_mean = (const double*)b->h_fc.data(); const double* h_depth = h_mean + nf;
+    const int* h_nobs = (const int*)(h_depth + nf); const int* h_rej = h_nobs + nf; const int* h_nrej = h_rej + nf;
+    const unsigned char* h_flags = (const unsigned char*)(h_nrej + nw);
+    if (n_feat) *n_feat = (int32_t)n;
+    if (mean_err) memcpy(mean_err, h_mean + f0, n * sizeof(double));
+    if (depth) memcpy(depth, h_depth + f0, n * sizeof(double));
+    if (n_obs) memcpy(n_obs, h_nobs + f0, n * sizeof(int));
+    if (flags) memcpy(flags, h_flags + f0, n);
+    if (rejected) memcpy(rejected, h_rej + f0, (size_t)h_nrej[w] * sizeof(int));
+    if (n_rejected) *n_rejected = h_nrej[w];
     return SWF_OK;
 }
 

@@ -57,6 +57,9 @@ struct swf_problem {
     std::vector<double> S, rhs, L;
     std::vector<double> mgA, mgb, mgJ, mgr0;      // swf_problem_marginalize outputs
     std::vector<double> tcA, tcQ;                 // swf_problem_tail_covariance outputs
+    // swf_problem_check_features outputs: the features' keys (landmarks in pool order, then the inverse depths ascending) and rows
+    bool fc_ok = false; std::vector<double*> fc_keys; std::unordered_map<const double*, int> fc_index;
+    std::vector<double> fc_mean, fc_depth; std::vector<int32_t> fc_nobs, fc_rej; std::vector<uint8_t> fc_flags;
     // composite IMU-GNSS factors, flattened
     std::vector<int32_t> comp_M, comp_N, comp_idx;
     std::vector<double> comp_pose, comp_sb, comp_pose_lin, comp_sb_lin, comp_Hpp, comp_HpN, comp_rhs_p, comp_HNN, comp_rhsN, comp_pre;
@@ -513,6 +516,7 @@ static void scatter_values(swf_problem* p) {     // Double2Vector direction; con
 int swf_problem_solve(swf_problem* p, const swf_options* opt, swf_summary* summary) {
     if (!p || !opt || !summary) return SWF_E_INVALID;
     int rc;
+    p->fc_ok = false;
     p->solved = false;                             // consumers (marginalize, tail covariance, get_reduced) answer only for a solve that went through
     const bool trace = getenv("SWF_TRACE_REBUILD") != nullptr;
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -570,6 +574,49 @@ int swf_problem_tail_covariance(swf_problem* p, const double** A, const double**
     p->tcA.assign((size_t)n * n, 0); p->tcQ.assign((size_t)n * n, 0);
     if ((rc = swf_batch_get_tail_covariance(p->batch, 0, p->tcA.data(), p->tcQ.data(), &n)) != SWF_OK) return rc;
     if (A) *A = p->tcA.data(); if (Qy) *Qy = p->tcQ.data(); if (n_out) *n_out = n;
+    return SWF_OK;
+}
+
+int swf_problem_check_features(swf_problem* p, double max_mean_error) {
+    if (!p) return SWF_E_INVALID;
+    if (!p->solved || !p->batch) return pfail(SWF_E_STATE, "swf_problem_check_features before swf_problem_solve");
+    p->fc_ok = false;
+    int rc;
+    if ((rc = swf_batch_check_features(p->batch, max_mean_error)) != SWF_OK) return rc;
+    int32_t n = 0, nr = 0;
+    if ((rc = swf_batch_get_feature_check(p->batch, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n)) != SWF_OK) return rc;
+    p->fc_keys = p->klm;
+    std::vector<int32_t> lams;
+    for (size_t i = 0; i < p->idp_kind.size(); i++) lams.push_back(p->idp_idx[5 * i + 4]);
+    std::sort(lams.begin(), lams.end());
+    lams.erase(std::unique(lams.begin(), lams.end()), lams.end());
+    for (int32_t c : lams) p->fc_keys.push_back(p->ksc[c]);
+    if ((int32_t)p->fc_keys.size() != n) return pfail(SWF_E_STATE, "swf_problem_check_features: feature count mismatch");
+    p->fc_mean.assign((size_t)n, 0); p->fc_depth.assign((size_t)n, 0); p->fc_nobs.assign((size_t)n, 0); p->fc_flags.assign((size_t)n, 0); p->fc_rej.assign((size_t)n, 0);
+    if ((rc = swf_batch_get_feature_check(p->batch, 0, p->fc_mean.data(), p->fc_depth.data(), p->fc_nobs.data(), p->fc_flags.data(),
+                                          p->fc_rej.data(), &nr, &n)) != SWF_OK) return rc;
+    p->fc_rej.resize((size_t)nr);
+    p->fc_index.clear();
+    for (int32_t i = 0; i < n; i++) p->fc_index[p->fc_keys[i]] = i;
+    p->fc_ok = true;
+    return SWF_OK;
+}
+
+int swf_problem_get_feature_check(swf_problem* p, const double* key, double* mean_err, double* depth, int32_t* n_obs, int32_t* flags) {
+    if (!p) return SWF_E_INVALID;
+    if (!p->fc_ok) return pfail(SWF_E_STATE, "swf_problem_get_feature_check before swf_problem_check_features (or after a new solve)");
+    auto it = p->fc_index.find(key);
+    if (it == p->fc_index.end()) return pfail(SWF_E_NOTFOUND, "swf_problem_get_feature_check: the key is no feature of the last solve");
+    const int i = it->second;
+    if (mean_err) *mean_err = p->fc_mean[i]; if (depth) *depth = p->fc_depth[i]; if (n_obs) *n_obs = p->fc_nobs[i]; if (flags) *flags = p->fc_flags[i];
+    return SWF_OK;
+}
+
+int swf_problem_rejected_features(swf_problem* p, double** keys, int32_t cap, int32_t* n) {
+    if (!p) return SWF_E_INVALID;
+    if (!p->fc_ok) return pfail(SWF_E_STATE, "swf_problem_rejected_features before swf_problem_check_features (or after a new solve)");
+    if (n) *n = (int32_t)p->fc_rej.size();
+    if (keys) for (int32_t i = 0; i < cap && i < (int32_t)p->fc_rej.size(); i++) keys[i] = p->fc_keys[p->fc_rej[i]];
     return SWF_OK;
 }
 

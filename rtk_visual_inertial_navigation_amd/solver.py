@@ -56,6 +56,8 @@ EXPORTED = [
     "swf_batch_create_on", "swf_batch_create_sharded", "swf_solve_batches", "swf_batch_device", "swf_default_options", "swf_shard_partition",
     "swf_prior_reset_linearization_point",
     "swf_lambda_batch", "swf_batch_ambiguity_search", "swf_batch_get_ambiguity_fix",
+    "swf_batch_check_features", "swf_batch_get_feature_check",
+    "swf_problem_check_features", "swf_problem_get_feature_check", "swf_problem_rejected_features",
 ]
 
 
@@ -230,6 +232,26 @@ class BatchSolver:
                  "swf_batch_get_ambiguity_fix")
             out.append(dict(F=F, s=sv, ratio=r, fixed=bool(fx.value), Qb=Qb, bf=bf, n_b=nb.value, info=info.value))
         return out
+
+    def check_features(self, threshold=2.0):
+        """The post-solve feature check of every window on the device (swf_batch_check_features: OutliersRejection's mean
+        reprojection error, R/swf/swf_image.cpp:255-308, and Double2Vector's depth sign, R/swf/swf.cpp:214-229) at the state
+        download_state() would return.  Features: the window's landmarks in pool order, then its inverse depths ascending.
+        Returns one dict per window: mean_err, depth, n_obs, flags (FEAT_* bits), rejected (ascending feature indices), n_feat."""
+        _chk(lib().swf_batch_check_features(self._h, C.c_double(threshold)), "swf_batch_check_features")
+        return [self.get_feature_check(w) for w in range(self.n)]
+
+    def get_feature_check(self, w=0):
+        pi = C.POINTER(C.c_int32)
+        nf, nr = C.c_int32(), C.c_int32()
+        _chk(lib().swf_batch_get_feature_check(self._h, C.c_int32(w), None, None, None, None, None, None, C.byref(nf)), "swf_batch_get_feature_check")
+        k = nf.value
+        m, d = np.zeros(k), np.zeros(k)
+        no, rj, fl = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.uint8)
+        _chk(lib().swf_batch_get_feature_check(self._h, C.c_int32(w), m.ctypes.data_as(_pd), d.ctypes.data_as(_pd), no.ctypes.data_as(pi),
+                                               fl.ctypes.data_as(C.POINTER(C.c_uint8)), rj.ctypes.data_as(pi), C.byref(nr), C.byref(nf)),
+             "swf_batch_get_feature_check")
+        return dict(mean_err=m, depth=d, n_obs=no, flags=fl, rejected=rj[:nr.value].copy(), n_feat=k)
 
     def enable_timing(self, mask=1):
         """mask: bit k brackets kernel K_NAMES[k] with a HIP event pair per launch (bit 0 = whole solve);
@@ -485,6 +507,24 @@ class Problem:
         n = n.value
         return dict(A=np.ctypeslib.as_array(A, (n, n)).copy(), Qy=np.ctypeslib.as_array(Q, (n, n)).copy(), n=n)
 
+    def CheckFeatures(self, threshold=2.0):
+        """SWFOptimization::OutliersRejection + the depth sign of Double2Vector after Solve (swf_problem_check_features).  Returns
+        (get, rejected): get(block) -> dict(mean_err, depth, n_obs, flags) by parameter block, rejected = the addresses of the
+        blocks FeatureManager::removeFailures would remove, in feature order."""
+        _chk(lib().swf_problem_check_features(self._h, C.c_double(threshold)), "CheckFeatures")
+        n = C.c_int32()
+        _chk(lib().swf_problem_rejected_features(self._h, None, C.c_int32(0), C.byref(n)), "CheckFeatures")
+        keys = (_pd * max(n.value, 1))()
+        _chk(lib().swf_problem_rejected_features(self._h, keys, n, C.byref(n)), "CheckFeatures")
+        rejected = [C.cast(keys[i], C.c_void_p).value for i in range(n.value)]
+
+        def get(arr):
+            m, d, no, fl = C.c_double(), C.c_double(), C.c_int32(), C.c_int32()
+            _chk(lib().swf_problem_get_feature_check(self._h, arr.ctypes.data_as(_pd), C.byref(m), C.byref(d), C.byref(no), C.byref(fl)),
+                 "swf_problem_get_feature_check")
+            return dict(mean_err=m.value, depth=d.value, n_obs=no.value, flags=fl.value)
+        return get, rejected
+
     def GetReduced(self):
         S, r, L, n = _pd(), _pd(), _pd(), C.c_int32()
         _chk(lib().swf_get_reduced(self._h, C.byref(S), C.byref(r), C.byref(L), C.byref(n)), "GetReduced")
@@ -730,6 +770,7 @@ def triangulate_batch(Ps, Rs, tic, ric, pbg, start_frame, pt0, pt1, init_depth=5
 
 
 LAMBDA_OK, LAMBDA_NOT_PD, LAMBDA_LOOP_LIMIT, LAMBDA_NO_INPUT = 0, 1, 2, 3
+FEAT_OUTLIER, FEAT_NEG_DEPTH, FEAT_UNOBSERVED = 1, 2, 4
 
 
 def lambda_batch(a_list, Q_list, m=2):
