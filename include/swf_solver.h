@@ -54,6 +54,10 @@ enum {
  * 108: no layout change; the post-solve feature check on the device: swf_batch_check_features / swf_batch_get_feature_check
  * (OutliersRejection's mean reprojection error and Double2Vector's depth sign per feature, the rejected list compacted on the
  * device), swf_problem_check_features / swf_problem_get_feature_check / swf_problem_rejected_features by parameter-block key.
+ * Round 8 (still 108, no ABI change): the final linearisation of an optimising solve forms the gradient alone (no group-0 inverses; the
+ * reduced system of that pass was never solved or exported).  Test aids read once at swf_batch_create, next to SWF_NO_SPEC_EVAL and the
+ * other launch-shape knobs: SWF_FULL_FINAL_ELIM=1 restores the complete elimination in that pass (bit-identical results);
+ * SWF_LS_GRAD_QPB=1|2|4|8|16 sets the landmark parts per workgroup of its landmark kernel (a measuring aid, as SWF_LS_QPB is).
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);

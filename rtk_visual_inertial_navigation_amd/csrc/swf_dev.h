@@ -59,6 +59,20 @@ struct GFac {
     int pad;                     // GF_PROJX: the caller's projection-factor index (row order of the Jacobian export)
 };
 
+// flat record of a scalar or an IMU factor for the J v products (jt_row_dot, swf_kernels.h): what sc_gf / imu_gf -> gf -> the slot arrays
+// hold about the factor, in one 96-byte load.  JT_MAXSLOT: the most parameter blocks a typed adder gives such a factor (an
+// inverse-depth projection between two cameras: two poses, two extrinsics, the inverse depth; an IMU factor has four).
+#define JT_MAXSLOT 5
+struct alignas(16) JtRec {
+    int win, nres, jld, nslot;
+    int roff, f, pad0, pad1;      // f: the factor's index in gf (g_aux)
+    int joff[JT_MAXSLOT];         // g_J offset of the slot's block, -1 where the slot has none (constant block, static clique)
+    int loc[JT_MAXSLOT];          // first local coordinate of the slot's block
+    int ls[JT_MAXSLOT];           // local size of the slot's block
+    int pad2;
+};
+static_assert(sizeof(JtRec) == 96, "JtRec: six 16-byte loads");
+
 // ---- clique: a group-0 block (or none) + the factors touching it + its reduced neighbours
 struct Clique {
     int win;
@@ -164,6 +178,7 @@ struct DevBatch {
     int n_imu; const int* imu_gf;              // generic-factor ids by kernel
     int n_idp; const int* idp_gf;              // two-row projection factors of the generic path: inverse-depth (GF_IDP) and world-point (GF_PROJX) ones (also members of sc_gf for the J v products)
     int n_sc;  const int* sc_gf;
+    const JtRec* sc_jt; const JtRec* imu_jt;    // flat J v records, one per entry of sc_gf / imu_gf
     int n_prior; const int* prior_gf;
     // priors.  A prior of more than PRIOR_SPLIT_DIM rows is evaluated by one workgroup per chunk of PRIOR_CHUNK rows (its n x n record is
     // n^2 doubles through ONE compute unit otherwise: 553 KB, 19 us per pass, for the 263-dimension marginalisation prior of BASELINE

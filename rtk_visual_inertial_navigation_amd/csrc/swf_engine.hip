@@ -260,6 +260,8 @@ struct swf_batch {
     bool L_full = false;                  // the L buffer holds the whole factor of the last linear solve
     int asm_programs = 0;                 // distinct assembly programs of the batch (windows of identical structure share one)
     int ls_qpb = 1, ls_var = 0, ls_kms = 8; bool ls_folded = false, s_direct = false;     // k_lm_schur launch shape, fixed at creation (the pair lists depend on it)
+    bool full_final = false;              // SWF_FULL_FINAL_ELIM=1: the solve's final linearisation runs the complete group-0 elimination, as every other one does (parity: bit-identical to the gradient-only pass)
+    int ls_gqpb = 4;                      // landmark parts per workgroup of the gradient-only landmark pass (it has no ring to fill: chosen for occupancy, not by ls_qpb)
     int timing = 0;                       // bitmask of SWF_K_* brackets
     swf_timing last{};
     std::vector<hipEvent_t> ev;           // event pool (pairs)
@@ -884,6 +886,7 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
     b->no_spec = getenv("SWF_NO_SPEC_EVAL") != nullptr;
     b->no_step_fuse = getenv("SWF_NO_STEP_FUSE") != nullptr;
     b->no_decide_fuse = getenv("SWF_NO_DECIDE_FUSE") != nullptr;
+    b->full_final = getenv("SWF_FULL_FINAL_ELIM") != nullptr;
     // auxiliary stream: the latency path (<= n_CU / 16 windows), and batches of half a chip to a chip of windows, where the IMU / clique branch
     // fills what one-block-per-window kernels leave idle (measured: 256 windows 5.52 -> 5.22 ms, 128 windows 3.73 -> 3.49 ms per solve; 64 and
     // 512 windows: no gain)
@@ -979,6 +982,11 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
         b->ls_var = (b->max_tiles <= 10 && force < 1) ? 0 : (b->max_tiles <= 36 && force < 2) ? 1 : (b->max_tiles <= 136 && force < 3) ? 2 : 3;
         b->ls_folded = qpb == GEMM_SPLIT && b->ls_var <= 1;          // must mirror CAN_FOLD in k_lm_schur
         b->s_direct = b->ls_folded;
+        // the gradient-only pass of the final linearisation: never more parts per workgroup than the product kernel takes (the latency path
+        // keeps its spread of a window over the chip).  SWF_LS_GRAD_QPB: test / measuring aid.
+        const int force_gqpb = getenv("SWF_LS_GRAD_QPB") ? atoi(getenv("SWF_LS_GRAD_QPB")) : 0;
+        b->ls_gqpb = std::min(qpb, LS_GRAD_QPB);
+        if (force_gqpb >= 1 && force_gqpb <= GEMM_SPLIT && (force_gqpb & (force_gqpb - 1)) == 0) b->ls_gqpb = force_gqpb;
     }
     {
         // k_lm_schur task table.  A wave task = the four 16-lane groups of one producer wave = four landmarks, one group and three of the
@@ -1082,6 +1090,27 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
     PUT(imu_pre, B.imu_pre); PUT(cp_dat, B.cp_dat); PUT(pr_dat, B.pr_dat); PUT(dop_dat, B.dop_dat); PUT(sp_w, B.sp_w); PUT(gx_dat, B.gx_dat);
     D.n_imu = (int)B.imu_gf.size(); D.n_sc = (int)B.sc_gf.size(); D.n_prior = (int)B.prior_gf.size();
     PUT(imu_gf, B.imu_gf); PUT(sc_gf, B.sc_gf); PUT(prior_gf, B.prior_gf); D.n_idp = (int)B.idp_gf.size(); PUT(idp_gf, B.idp_gf);
+    {   // flat J v records of the scalar and the IMU factors (JtRec, swf_dev.h): the factor and its slots as the tables above hold them
+        bool fits = true;
+        auto jt_recs = [&](const std::vector<int>& list) {
+            std::vector<JtRec> out(list.size());
+            for (size_t q = 0; q < list.size(); q++) {
+                const GFac& G = B.gf[(size_t)list[q]];
+                JtRec& r = out[q];
+                r = JtRec{};
+                r.win = G.win; r.nres = G.nres; r.jld = G.jld; r.nslot = G.nslot; r.roff = G.roff; r.f = list[q];
+                if (G.nslot > JT_MAXSLOT) { fits = false; continue; }
+                for (int t = 0; t < JT_MAXSLOT; t++) {
+                    const bool has = t < G.nslot;
+                    r.joff[t] = has ? B.s_joff[(size_t)G.slot0 + t] : -1; r.loc[t] = has ? B.s_loc[(size_t)G.slot0 + t] : 0; r.ls[t] = has ? B.s_ls[(size_t)G.slot0 + t] : 0;
+                }
+            }
+            return out;
+        };
+        const std::vector<JtRec> sj = jt_recs(B.sc_gf), ij = jt_recs(B.imu_gf);
+        if (!fits) { P.release(); delete b; return fail(SWF_E_UNSUPPORTED, "scalar / IMU factor with more than JT_MAXSLOT parameter blocks"); }
+        PUT(sc_jt, sj); PUT(imu_jt, ij);
+    }
     PUT(prior_dim, B.prior_dim); PUT(prior_Joff, B.prior_Joff); PUT(prior_roff, B.prior_roff); PUT(prior_x0off, B.prior_x0off);
     {   // transposed copies of the prior records for the J v products
         std::vector<double> Jt(B.prior_J.size());
@@ -1636,13 +1665,18 @@ struct Launcher {
             if (D.n_clc[3]) {
                 // class 3 next to class 2 in one grid; class 4 (other factors of the batch with fewer ambiguities) on its own
                 hipLaunchKernelGGL(k_clique_big2, dim3(D.n_clc[3] + D.n_clc[2]), dim3(CB_NT), 0, st, D, O);
-                if (D.n_clc[4]) hipLaunchKernelGGL(k_clique_tall, dim3(D.n_clc[4]), dim3(256), 0, st, D, O);
+                if (D.n_clc[4]) hipLaunchKernelGGL(k_clique_tall<false>, dim3(D.n_clc[4]), dim3(256), 0, st, D, O);
             } else if (D.n_clc[4] + D.n_clc[2]) hipLaunchKernelGGL(k_clique_tall2, dim3(D.n_clc[4] + D.n_clc[2]), dim3(256), 0, st, D, O);
         } else if (D.n_lm) {
             Bracket t(*this, write_S ? SWF_K_LM_SCHUR : SWF_K_LM_ELIM);
             lm_qpb = b->ls_qpb; lm_folded = b->ls_folded;
-            if (!write_S) {
-                // cost / gradient pass (the solve's final linearisation): the elimination alone — producer waves only, no panel
+            if (!write_S && !b->full_final) {
+                // cost / gradient pass (the solve's final linearisation; k_finalize reads the gradient alone): g, diag and vc of the landmarks —
+                // producer waves only, no panel, no inverse, at a workgroup size of its own
+                dim3 grid(D.n_win, GEMM_SPLIT / b->ls_gqpb);
+                hipLaunchKernelGGL((k_lm_schur<8, 2, 2, 80, false, true>), grid, dim3(256), 0, st, D, O, b->ls_gqpb, 0, 0, 0);
+            } else if (!write_S) {
+                // (SWF_FULL_FINAL_ELIM: the elimination alone, Einv and g_l included)
                 dim3 grid(D.n_win, GEMM_SPLIT / lm_qpb);
                 hipLaunchKernelGGL((k_lm_schur<8, 2, 2, 80, false>), grid, dim3(256), 0, st, D, O, lm_qpb, 0, 0, 0);
             } else {
@@ -1662,15 +1696,33 @@ struct Launcher {
             if (comp_fused) {
                 for (; lm_next < b->max_tiles; lm_next += ls_tiles_per_launch()) { Bracket t(*this, SWF_K_LM_SCHUR, sa); lm_launch(lm_next, sa); }
             } else {
-            if (D.n_clc[1]) { Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(1)); hipLaunchKernelGGL((k_clique_elim<32, 48, 9, 1>), dim3(D.n_clc[1]), dim3(64), 0, cstream(1), D, O); }
-            if (D.n_clc[0]) { Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(0)); hipLaunchKernelGGL((k_clique_elim<48, 32, 1, 0>), dim3(D.n_clc[0]), dim3(64), 0, cstream(0), D, O); }
+            // (the final linearisation: the gradient-only instantiations of the same function; k_clique_big has none and runs in full)
+            const bool grad = !write_S && !b->full_final;
+            if (D.n_clc[1]) {
+                Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(1));
+                if (grad) hipLaunchKernelGGL((k_clique_elim<32, 48, 9, 1, true>), dim3(D.n_clc[1]), dim3(64), 0, cstream(1), D, O);
+                else hipLaunchKernelGGL((k_clique_elim<32, 48, 9, 1>), dim3(D.n_clc[1]), dim3(64), 0, cstream(1), D, O);
+            }
+            if (D.n_clc[0]) {
+                Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(0));
+                if (grad) hipLaunchKernelGGL((k_clique_elim<48, 32, 1, 0, true>), dim3(D.n_clc[0]), dim3(64), 0, cstream(0), D, O);
+                else hipLaunchKernelGGL((k_clique_elim<48, 32, 1, 0>), dim3(D.n_clc[0]), dim3(64), 0, cstream(0), D, O);
+            }
             if (D.n_clc[2] && !clq_fused) {
                 Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(2));
-                if (b->lat_fuse) hipLaunchKernelGGL(k_clique_elim4, dim3(D.n_clc[2]), dim3(256), 0, cstream(2), D, O);      // latency form: four waves per clique, same bits
+                if (b->lat_fuse) {      // latency form: four waves per clique, same bits
+                    if (grad) hipLaunchKernelGGL(k_clique_elim4<true>, dim3(D.n_clc[2]), dim3(256), 0, cstream(2), D, O);
+                    else hipLaunchKernelGGL(k_clique_elim4<false>, dim3(D.n_clc[2]), dim3(256), 0, cstream(2), D, O);
+                }
+                else if (grad) hipLaunchKernelGGL((k_clique_elim<64, 64, 9, 2, true>), dim3(D.n_clc[2]), dim3(64), 0, cstream(2), D, O);
                 else hipLaunchKernelGGL((k_clique_elim<64, 64, 9, 2>), dim3(D.n_clc[2]), dim3(64), 0, cstream(2), D, O);
             }
             if (D.n_clc[3]) { Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(3)); hipLaunchKernelGGL(k_clique_big, dim3(D.n_clc[3]), dim3(CB_NT), 0, cstream(3), D, O); }
-            if (D.n_clc[4]) { Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(4)); hipLaunchKernelGGL(k_clique_tall, dim3(D.n_clc[4]), dim3(256), 0, cstream(4), D, O); }
+            if (D.n_clc[4]) {
+                Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(4));
+                if (grad) hipLaunchKernelGGL(k_clique_tall<true>, dim3(D.n_clc[4]), dim3(256), 0, cstream(4), D, O);
+                else hipLaunchKernelGGL(k_clique_tall<false>, dim3(D.n_clc[4]), dim3(256), 0, cstream(4), D, O);
+            }
             if (write_S && D.n_lm) {
                 // further tile ranges write nothing but their tiles of P (k_lm_schur: outs), so on the latency path they run behind the
                 // IMU / clique branch, next to the first range

@@ -880,35 +880,66 @@ __device__ __forceinline__ double gf_row_dot(const DevBatch& B, const DevOpt& O,
     return a;
 }
 template <int MODE>
-__device__ __forceinline__ double gf_row_term(const DevBatch& B, const GFac& G, int k, double a) {
-    return MODE == 0 ? a * a : a * (B.g_r[G.roff + k] + a / 2.0);
+__device__ __forceinline__ double gf_row_term(const DevBatch& B, int roff, int k, double a) {
+    return MODE == 0 ? a * a : a * (B.g_r[roff + k] + a / 2.0);
 }
-// scalar (one-row) factors: one lane each
+template <int MODE>
+__device__ __forceinline__ double gf_row_term(const DevBatch& B, const GFac& G, int k, double a) { return gf_row_term<MODE>(B, G.roff, k, a); }
+// Row k of (J v) for a scalar or an IMU factor, from the factor's flat record (JtRec, swf_dev.h: the host built it from the GFac and
+// its slots, so the addressing is ONE load level deep instead of sc_gf -> gf -> slot arrays).  The factor's columns are walked flat,
+// slot after slot (a slot without a Jacobian block takes no columns), CH at a time: every Jacobian element and every vector entry
+// of the round is requested unconditionally, the columns beyond the factor's last clamped to element 0, before the first is used.
+// The sum is the one gf_row_dot forms: slots in order, columns in order, a += c * v.
+template <int MODE, int CH = 16>
+__device__ __forceinline__ double jt_row_dot(const DevBatch& B, const DevOpt& O, const JtRec& R, int k) {
+    int e[JT_MAXSLOT], ncol = 0;                         // e[t]: end of slot t in the flat column order
+#pragma unroll
+    for (int t = 0; t < JT_MAXSLOT; t++) { ncol += (t < R.nslot && R.joff[t] >= 0) ? R.ls[t] : 0; e[t] = ncol; }
+    double a = 0;
+    for (int u0 = 0; u0 < ncol; u0 += CH) {
+        double c[CH], v[CH];
+#pragma unroll
+        for (int j = 0; j < CH; j++) {
+            const int u = u0 + j;
+            int jo = R.joff[0], lo = R.loc[0], st = 0;
+#pragma unroll
+            for (int t = 1; t < JT_MAXSLOT; t++) if (u >= e[t - 1]) { jo = R.joff[t]; lo = R.loc[t]; st = e[t - 1]; }
+            const bool ok = u < ncol;                    // (then the slot found has columns, and with them a Jacobian block)
+            c[j] = B.g_J[ok ? jo + (u - st) * R.jld + k : 0];
+            v[j] = vec_at<MODE>(B, O, ok ? lo + (u - st) : 0);
+        }
+#pragma unroll
+        for (int j = 0; j < CH; j++) if (u0 + j < ncol) a += c[j] * v[j];
+    }
+    return a;
+}
+// scalar (one-row) factors: one lane each.  Load levels: the record; then the window's gate flag next to the row's Jacobian
+// elements and vector entries (lanes beyond the last factor repeat its loads); the gate comes last.
 template <int MODE>
 __device__ __forceinline__ void d_jtimes_scalar(const DevBatch& B, const DevOpt& O, int bid) {
     int q = bid * blockDim.x + threadIdx.x;
-    if (q >= B.n_sc) return;
-    int f = B.sc_gf[q];
-    const GFac& G = B.gf[f];
-    const WinState& s = B.ws[G.win];
-    if (MODE == 0 ? !s.need_lin : !s.eval_cand) return;
+    const bool valid = q < B.n_sc;
+    const JtRec R = B.sc_jt[valid ? q : B.n_sc - 1];
+    const WinState& s = B.ws[R.win];
+    const int gate = MODE == 0 ? s.need_lin : s.eval_cand;
     double a = 0;
-    for (int k = 0; k < G.nres; k++) a += gf_row_term<MODE>(B, G, k, gf_row_dot<MODE>(B, O, G, k));     // nres = 1, or 2 for the inverse-depth projections
-    B.g_aux[f] = a;
+    for (int k = 0; k < R.nres; k++) a += gf_row_term<MODE>(B, R.roff, k, jt_row_dot<MODE>(B, O, R, k));     // nres = 1, or 2 for the inverse-depth projections
+    if (valid && gate) B.g_aux[R.f] = a;
 }
-// IMU factors: 16 lanes per factor, one residual row per lane
+// IMU factors: 16 lanes per factor, one residual row per lane (lane 15 repeats row 14's loads and contributes nothing)
 template <int MODE>
 __device__ __forceinline__ void d_jtimes_imu(const DevBatch& B, const DevOpt& O, int bid) {
     int q = (bid * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15;
-    bool valid = q < B.n_imu;
-    int f = B.imu_gf[valid ? q : B.n_imu - 1];
-    const GFac& G = B.gf[f];
-    const WinState& s = B.ws[G.win];
-    bool act = valid && (MODE == 0 ? s.need_lin : s.eval_cand);
-    double part = 0;
-    if (act && sub < 15) part = gf_row_term<MODE>(B, G, sub, gf_row_dot<MODE>(B, O, G, sub));
+    const bool valid = q < B.n_imu;
+    const JtRec R = B.imu_jt[valid ? q : B.n_imu - 1];
+    const WinState& s = B.ws[R.win];
+    const int gate = MODE == 0 ? s.need_lin : s.eval_cand;
+    const int k = sub < 15 ? sub : 14;
+    double part = gf_row_term<MODE>(B, R.roff, k, jt_row_dot<MODE>(B, O, R, k));
+    const bool act = valid && gate;
+    if (!(act && sub < 15)) part = 0;
     part = grp16_sum(part);
-    if (act && sub == 0) B.g_aux[f] = part;
+    if (act && sub == 0) B.g_aux[R.f] = part;
 }
 // priors: one 256-thread workgroup per prior, threads over residual rows.  The vector entries at the prior's columns (the same for every
 // row) are staged in LDS once together with the column -> local index map, so a row's dot product is n coalesced loads of the transposed
@@ -1013,7 +1044,10 @@ __device__ unsigned long long g_clq_stamps[16];
 // phases whose work is a set of independent output elements — the gather, the rows of M_e*, the 2x2 blocks of C — are dealt over
 // 4 waves; the Gauss-Jordan inverse and the columns of T stay on wave 0.  Every output element is still formed by ONE lane with the
 // same operands in the same order, so the two forms give the same bits (tested: a window alone vs inside a large batch).
-template <int MAXR, int MAXD, int MAXE, int CLS, int PF = 24, int NW = 1, int UK = 4>      // UK: unrolling of the k loops (register budget)
+// GRAD: the gradient-only form, for the solve's final linearisation (its reduced system is never solved; k_finalize reads g alone).  The
+// same gather and the same column loop without the rows of M_e*: g / diag / vc of the eliminated block and graw / dgraw of the members
+// come out bit for bit as above, and the function ends there — no inverse, T, cE, cv_cs or C, and no lin_fail from a pivot.
+template <int MAXR, int MAXD, int MAXE, int CLS, int PF = 24, int NW = 1, int UK = 4, bool GRAD = false>      // UK: unrolling of the k loops (register budget)
 __device__ __forceinline__ void d_clique_elim(const DevBatch& B, const DevOpt& O, const int cidx_) {
     constexpr int LD = MAXD + 1, NT = 64 * NW;
     __shared__ double Jc[MAXR][LD];                 // dense clique Jacobian: rows = residual rows, cols = [e | members]
@@ -1062,6 +1096,7 @@ __device__ __forceinline__ void d_clique_elim(const DevBatch& B, const DevOpt& O
     }
     __syncthreads();
     QST(1);
+    if (GRAD && wq != 0) return;                    // (g_c and M_cc are wave 0's, and no barrier follows in this form)
     // lane c < d: column c of M_e* (k-ascending dot products), gradient entry g_c, and the diagonal M_cc.  NW > 1: wave q forms the rows
     // a2 = q, q + NW, ... of M_e*; g_c and M_cc are wave 0's.
     double me[MAXE], gc = 0, mcc = 0;
@@ -1074,8 +1109,10 @@ __device__ __forceinline__ void d_clique_elim(const DevBatch& B, const DevOpt& O
             for (int k = 0; k < nrow; k++) {
                 double x = Jc[k][c];
                 gc += x * rv[k]; mcc += x * x;
+                if (!GRAD) {
 #pragma unroll
                 for (int a2 = 0; a2 < MAXE; a2++) me[a2] += Jc[k][a2] * x;      // (rows a2 >= d_e are computed and dropped)
+                }
             }
         } else {
             constexpr int RPW = (MAXE + NW - 1) / NW;                          // rows of M_e* per wave
@@ -1083,27 +1120,30 @@ __device__ __forceinline__ void d_clique_elim(const DevBatch& B, const DevOpt& O
             for (int k = 0; k < nrow; k++) {
                 double x = Jc[k][c];
                 if (wq == 0) { gc += x * rv[k]; mcc += x * x; }
+                if (!GRAD) {
 #pragma unroll
                 for (int u = 0; u < RPW; u++) { int a2 = wq + u * NW; if (a2 < MAXE) me[u] += Jc[k][a2] * x; }
+                }
             }
         }
     }
     if (lane < d) {
         // rows >= d_e of Me / Ei / T are kept at zero so the inner loops below need no d_e guards
-        if (NW == 1) {
+        if (!GRAD && NW == 1) {
 #pragma unroll
             for (int a2 = 0; a2 < MAXE; a2++) Me[a2][lane] = a2 < de ? me[a2] : 0.0;
-        } else {
+        } else if (!GRAD) {
             constexpr int RPW = (MAXE + NW - 1) / NW;
 #pragma unroll
             for (int u = 0; u < RPW; u++) { int a2 = wq + u * NW; if (a2 < MAXE) Me[a2][lane] = a2 < de ? me[u] : 0.0; }
         }
         if (wq == 0) {
-            if (NW > 1) gcs[lane] = gc;
+            if (NW > 1 && !GRAD) gcs[lane] = gc;
             if (lane < de) { B.g[C.e_loc + lane] = gc; B.diag[C.e_loc + lane] = mcc; B.vc[C.e_loc + lane] = gc / clampd(mcc, O.min_diag, O.max_diag); }
             else { B.cv_graw[C.v_off + lane - de] = gc; B.cv_dgraw[C.v_off + lane - de] = mcc; }
         }
     }
+    if (GRAD) return;
     __syncthreads();
     QST(2);
     if (de > 0) {
@@ -1259,15 +1299,18 @@ __device__ __forceinline__ void d_clique_elim(const DevBatch& B, const DevOpt& O
     }
     QST(5);
 }
-template <int MAXR, int MAXD, int MAXE, int CLS>
-__global__ void __launch_bounds__(64) k_clique_elim(DevBatch B, DevOpt O) { d_clique_elim<MAXR, MAXD, MAXE, CLS>(B, O, (int)blockIdx.x); }
+// (GRAD: the gradient-only instantiations of the final linearisation, under kernel names of their own)
+template <int MAXR, int MAXD, int MAXE, int CLS, bool GRAD = false>
+__global__ void __launch_bounds__(64) k_clique_elim(DevBatch B, DevOpt O) { d_clique_elim<MAXR, MAXD, MAXE, CLS, 24, 1, 4, GRAD>(B, O, (int)blockIdx.x); }
 // the latency form as a kernel of its own: four waves per clique (batches too large for the fused grid below, but still on the latency path)
-__global__ void __launch_bounds__(256) k_clique_elim4(DevBatch B, DevOpt O) { d_clique_elim<64, 64, 9, 2, 8, 4>(B, O, (int)blockIdx.x); }
+template <bool GRAD = false>
+__global__ void __launch_bounds__(256) k_clique_elim4(DevBatch B, DevOpt O) { d_clique_elim<64, 64, 9, 2, 8, 4, 4, GRAD>(B, O, (int)blockIdx.x); }
 // class 4: up to 96 rows x 64 columns — the clique of a speed-bias block that two composite IMU-GNSS factors touch (the reference's own
 // ordering puts every other speed-bias block into group 0, R/swf/swf_gnss.cpp:683-691: 2 x (30 + N) rows, 9 + 6 + 9 + 6 + 6 + 9 + N
 // columns: N <= 18 ambiguities fit 96 rows x 64 columns, more take k_clique_big).  The four-wave form of the same function.
 #define CLQ_TALLR 96
-__global__ void __launch_bounds__(256) k_clique_tall(DevBatch B, DevOpt O) { d_clique_elim<CLQ_TALLR, 64, 9, 4, 8, 4>(B, O, (int)blockIdx.x); }
+template <bool GRAD = false>
+__global__ void __launch_bounds__(256) k_clique_tall(DevBatch B, DevOpt O) { d_clique_elim<CLQ_TALLR, 64, 9, 4, 8, 4, 4, GRAD>(B, O, (int)blockIdx.x); }
 
 // Latency path: the landmark Schur complement and the clique eliminations are independent of each other (both follow the factor
 // evaluation, both feed the assembly) — ONE grid of 1024-thread workgroups runs both: rows [0, n_parts) of the grid are k_lm_schur's

@@ -45,6 +45,7 @@ __device__ unsigned long long g_gemm_stamps[16];
 #define GSTAMP_ACC(i, t0)
 #define GNOW() 0ULL
 #endif
+#define LS_GRAD_QPB 4                         // landmark parts per workgroup of the gradient-only pass (GRAD below) in batches
 #define LS_NB 4                               // ring buffers = producer teams
 #define LS_NT(NCW, TW) ((LS_NB * (TW) + (NCW)) * 64)
 #define LS_MAXF 64                            // observing frames per window (64-bit frame masks)
@@ -53,7 +54,8 @@ __device__ unsigned long long g_gemm_stamps[16];
 //   <8, 2, 2,  80>   <= 10 frames  (<= 10 tiles)            <8, 5, 2, 144>   <= 21 frames (<= 36 tiles)
 //   <12, 6, 1, 272>  <= 42 frames  (<= 136 tiles, 2 launches of 72)    <12, 6, 1, 400>  <= 64 frames (<= 300 tiles, 5 launches)
 // GEMM = false: the elimination alone (g_l, diag, Einv for a cost / gradient pass: the solve's last linearisation, whose system
-// is never solved): producer waves only, no panel, under its own kernel name.
+// is never solved): producer waves only, no panel, under its own kernel name.  GRAD (with GEMM = false): g_l, diag and vc alone — no
+// damping, no 3x3 inverse, no Einv / g_l record (only the back-substitution reads those, and none follows the final linearisation).
 struct LsRec { int L, loc, o0, o1, col, info; };            // o0 .. o1: the landmark's observations (<= 64); col = first column of the landmark within its wave's twelve (0, 3, 6, 9)
 struct LsDat { double jl[6], rr[2]; int f; };
 __device__ __forceinline__ void ls_wait(const unsigned* flag, unsigned target, WinState& s) {
@@ -73,8 +75,9 @@ __device__ __forceinline__ void ls_signal(unsigned* flag) {
 }
 // (the kernel's body as a device function of the block coordinates: k_lm_schur below, and — latency path — the landmark workgroups of the
 // fused elimination grid k_lm_clique in swf_kernels.h)
-template <int NCW, int TPW, int TW, int LDR, bool GEMM>
+template <int NCW, int TPW, int TW, int LDR, bool GEMM, bool GRAD = false>
 __device__ __forceinline__ void d_lm_schur(const DevBatch& B, const DevOpt& O, int qpb, int lp, int kms, int s_direct, const int bx_, const int by_) {
+    static_assert(!(GEMM && GRAD), "the gradient-only form has no product");
     constexpr int NPW = GEMM ? LS_NB * TW : 4;                         // producer waves
     constexpr int NCOL = 12 * TW, NG = TW;                             // columns / wave tasks per chunk
     constexpr int PANEL = NCOL * LDR;                                  // doubles per buffer
@@ -370,7 +373,7 @@ __device__ __forceinline__ void d_lm_schur(const DevBatch& B, const DevOpt& O, i
             B.vc[loc] = g0 * rcp_nr(clampd(h00, O.min_diag, O.max_diag)); B.vc[loc + 1] = g1 * rcp_nr(clampd(h11, O.min_diag, O.max_diag)); B.vc[loc + 2] = g2 * rcp_nr(clampd(h22, O.min_diag, O.max_diag));
         }
         double i00 = 0, i11 = 0, i22 = 0, i10 = 0, i20 = 0, i21 = 0;
-        if (act) {
+        if (act && !GRAD) {
             const bool jfirst = s.iter == 0;
             h00 = __builtin_fma(mu, damp_diag(O, h00, B.jsc + loc, jfirst), h00);
             h11 = __builtin_fma(mu, damp_diag(O, h11, B.jsc + loc + 1, jfirst), h11);
@@ -485,7 +488,7 @@ __device__ __forceinline__ void d_lm_schur(const DevBatch& B, const DevOpt& O, i
     if (wv == 0) GSTAMP_ACC(6, tall);
     }
 }
-template <int NCW, int TPW, int TW, int LDR, bool GEMM>
+template <int NCW, int TPW, int TW, int LDR, bool GEMM, bool GRAD = false>
 __global__ void __launch_bounds__(GEMM ? LS_NT(NCW, TW) : 256) k_lm_schur(DevBatch B, DevOpt O, int qpb, int lp, int kms, int s_direct) {
-    d_lm_schur<NCW, TPW, TW, LDR, GEMM>(B, O, qpb, lp, kms, s_direct, (int)blockIdx.x, (int)blockIdx.y);
+    d_lm_schur<NCW, TPW, TW, LDR, GEMM, GRAD>(B, O, qpb, lp, kms, s_direct, (int)blockIdx.x, (int)blockIdx.y);
 }
