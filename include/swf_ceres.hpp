@@ -535,6 +535,27 @@ inline int lambda(int n, int m, const double* a, const double* Q, double* F, dou
     return 0;
 }
 
+// Fix and hold: the second half of SWFOptimization::LambdaSearch (R/swf/swf_lambda.cpp:254-353) on the device.  The reference builds a
+// MarginalizationInfo from last_marg_info, adds FixedIntegerFactor(ROUND(F), 1 / 0.03) per double difference and
+// FixedIntegerFactor(0, 1 / 0.03) per reference ambiguity on the hidden tf offsets, marginalises the tf and makes the result the new
+// last_marg_info.  Here: `prior` = the window prior's residual block, amb[i] / ref[i] = the two ambiguity blocks of double difference i,
+// N21[i] = ROUND(F[i]).  scalars_at_zero = true (the default, as in the Python bindings) evaluates every one-dimensional kept block at 0,
+// which is what the reference has between PhaseBiasSaveAndReset and PhaseBiasRestore: the call gives the reference's prior wherever it
+// is made, inside that bracket or without it.  false reads those blocks at their current values (the same quadratic).  On success *out holds the new
+// (linearized_jacobians, linearized_residuals) and x0 the new keep_block_data, solver-owned until the next call; the caller swaps the
+// prior as the reference does (:344-354): RemoveResidualBlock(prior), AddResidualBlock(new MarginalizationFactor(J, r0, x0, n, ...)).
+inline bool FixAndHoldPrior(Problem* p, ResidualBlockId prior, const std::vector<double*>& amb, const std::vector<double*>& ref,
+                            const std::vector<double>& N21, MarginalPrior* out, const double** x0, bool scalars_at_zero = true,
+                            double istd = 1.0 / 0.03, bool eigen = true, double eps = 1e-8) {
+    if (!p || !prior || !out || amb.empty() || amb.size() != ref.size() || amb.size() != N21.size()) return false;
+    int32_t n = 0, rank = 0;
+    const int rc = swf_problem_fix_prior(p->handle(), prior->id, amb.data(), ref.data(), N21.data(), (int32_t)amb.size(), scalars_at_zero ? 1 : 0,
+                                         istd, eps, eigen ? SWF_PRIOR_EIGEN : SWF_PRIOR_CHOLESKY, &out->linearized_jacobians,
+                                         &out->linearized_residuals, x0, &n, &rank);
+    out->A = nullptr; out->b = nullptr; out->n = n; out->rank = rank;
+    return rc == SWF_OK && rank >= 0;
+}
+
 // SWFOptimization::OutliersRejection (R/swf/swf_image.cpp:263-308) together with the depth-sign test of Double2Vector
 // (R/swf/swf.cpp:214-229), on the device, after Solve: `failed` receives the parameter blocks (landmarks / inverse depths) whose
 // mean reprojection error times FOCAL_LENGTH / FEATUREWEIGHTINVERSE exceeds `threshold` (the reference: 2) or whose depth is

@@ -58,6 +58,10 @@ enum {
  * reduced system of that pass was never solved or exported).  Test aids read once at swf_batch_create, next to SWF_NO_SPEC_EVAL and the
  * other launch-shape knobs: SWF_FULL_FINAL_ELIM=1 restores the complete elimination in that pass (bit-identical results);
  * SWF_LS_GRAD_QPB=1|2|4|8|16 sets the landmark parts per workgroup of its landmark kernel (a measuring aid, as SWF_LS_QPB is).
+ * 109: no layout change; fix and hold on the device: swf_prior_fix_batch (stand-alone: a linear prior plus fixed-integer constraints whose
+ * hidden offsets are eliminated in closed form, re-rooted), swf_batch_fix_prior / swf_batch_get_fixed_prior / swf_batch_install_fixed_prior
+ * (the second half of LambdaSearch behind swf_batch_ambiguity_search, the new prior written into the resident batch without a rebuild),
+ * swf_problem_fix_prior by parameter-block key.  A linear prior may keep blocks of the parameter_head tail.
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);
@@ -209,10 +213,45 @@ int swf_batch_get_tail_covariance(swf_batch* b, int32_t w, double* A, double* Qy
  * Qb [n_b][n_b] row-major and bf [n_b] (the search's own inputs, so that a caller can replay them), n_b, info (SWF_LAMBDA_*).
  * ratio / fixed are 0 unless info == SWF_LAMBDA_OK.  The search results are invalidated by the next swf_batch_solve
  * (SWF_E_STATE).  Stays with the caller: the choice of the reference satellites and the fractional-part gating of D's rows (:163),
- * the early returns on too few rows (:178, :184), the fix counter and the new prior of FixedIntegerFactors (:250-, swf_add_fixed_integer). */
+ * the early returns on too few rows (:178, :184) and the fix counter.  The new prior of FixedIntegerFactors (:250-355) is
+ * swf_batch_fix_prior below. */
 int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_first, const int32_t* pairs, double ratio_threshold);
 int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, double* s, double* ratio, int32_t* fixed,
                                 double* Qb, double* bf, int32_t* n_b, int32_t* info);
+
+/* Fix and hold: the second half of SWFOptimization::LambdaSearch (R/swf/swf_lambda.cpp:249-355) for every window, on the device.  The
+ * reference builds a MarginalizationInfo from the window prior, adds FixedIntegerFactor(ROUND(F), 1/0.03) per double difference and
+ * FixedIntegerFactor(0, 1/0.03) per reference ambiguity, both on a hidden offset tf per (system, frequency), eliminates the tf with
+ * marginalize(false, true) and makes the result the window prior.  Here (the operator of swf_prior_fix_batch, which see): needs a
+ * swf_batch_ambiguity_search after the last solve (SWF_E_STATE otherwise); asynchronous on the batch stream.
+ *   prior_sel [n_windows]  which LINEAR prior of the window to update (index among swf_flat_window::n_prior; NULL = prior 0).  A window
+ *                          has no such prior (a composite factor's record is none): SWF_E_INVALID; its dimension > 140: SWF_E_UNSUPPORTED.
+ *   n_use [n_windows]      take the first n_use[w] pairs of the search (NULL = all; the reference takes the newest epoch's, last_count)
+ *   enable [n_windows]     0 = leave the window alone (NULL = all enabled; the host's fix counter stays with the caller)
+ * Rows of window w, from the search's own device buffers: pair i < n_use[w] = (a, b) gives (coordinate of a, group b, v = ROUND(F1[i]));
+ * every distinct b gives (coordinate of b, group b, v = 0).  A tail coordinate whose block the prior does not keep, or rows the operator
+ * rejects (one coordinate twice): SWF_E_INVALID at the call, before anything is enqueued.  A window is APPLIED iff it is enabled with
+ * n_use > 0, the search's info == SWF_LAMBDA_OK, and (ignore_ratio || fixed) — fixed is read on the device.  The prior's residual is
+ * evaluated at the state swf_batch_download_state would return at that moment; scalars_at_zero != 0 evaluates every one-dimensional kept
+ * block at 0 and returns 0 as its new linearisation point (PhaseBiasSaveAndReset / PhaseBiasRestore around the reference's call); with
+ * scalars_at_zero == 0 the rows' values are taken relative to the scalars' current values (the prior and the constraints are linear in
+ * scalars, so both settings describe the same quadratic).  Read-only until installed: a solve, export, marginalisation or
+ * search issued afterwards is bit-identical with and without the call.
+ * swf_batch_get_fixed_prior synchronises; its first call copies every window's results in one transfer per array.  A / J n x n row-major,
+ * bv / r0 / eig n, x0 = the new linearisation point (global sizes concatenated in kept-block order), n = the prior's dimension, rank as
+ * swf_batch_marginalize reports it (SWF_PRIOR_CHOLESKY on a singular A': -1 and not applied), applied 0 / 1.  Arrays of a window that was
+ * not applied are not written.  Any pointer may be NULL.  Results are invalidated by the next swf_batch_solve or search (SWF_E_STATE).
+ * swf_batch_install_fixed_prior writes (J', r0', x0') of every applied window into the batch's own record of that prior and everything
+ * derived from it (the transposed record, the static prior clique's C = J^T J and its diagonal, accumulated in swf_batch_create's order:
+ * the batch equals one freshly created with the new prior bit for bit); windows that were not applied keep their prior bit for bit.  The
+ * next swf_batch_solve runs with the fix-and-hold prior, without a rebuild.  An install is a change of the batch's STRUCTURE data, not of
+ * its state: swf_batch_upload_state and swf_batch_reset_state do not undo it (the windows' own prior_J / prior_r0 / prior_x0 arrays are
+ * not touched either: fetch the new prior with the getter if the host keeps a copy). */
+int swf_batch_fix_prior(swf_batch* b, const int32_t* prior_sel, const int32_t* n_use, const uint8_t* enable, int32_t ignore_ratio,
+                        int32_t scalars_at_zero, double istd, double eps, int32_t form);
+int swf_batch_get_fixed_prior(swf_batch* b, int32_t w, double* A, double* bv, double* J, double* r0, double* x0, double* eig,
+                              int32_t* n, int32_t* rank, int32_t* applied);
+int swf_batch_install_fixed_prior(swf_batch* b);
 
 /* Post-solve feature check: what the reference does to every feature after every window solve — the depth-sign test of
  * SWFOptimization::Double2Vector (R/swf/swf.cpp:214-229) and the mean reprojection error of OutliersRejection
@@ -315,6 +354,33 @@ int swf_preintegrate_batch(const double* samples, const int32_t* first, int32_t 
 enum { SWF_LAMBDA_OK = 0, SWF_LAMBDA_NOT_PD = 1, SWF_LAMBDA_LOOP_LIMIT = 2, SWF_LAMBDA_NO_INPUT = 3 };
 int swf_lambda_batch(int32_t n_problems, int32_t ld, const int32_t* n, const double* a, const double* Q,
                      int32_t m, double* F, double* s, int32_t* info, int32_t on_device, void* stream);
+
+/* Fix and hold as a stand-alone operator: n linear priors, each with a list of fixed-integer constraint rows whose hidden per-group
+ * offsets are eliminated (FixedIntegerFactor + marginalize(false, true), R/swf/swf_lambda.cpp:254-343), re-rooted.  One workgroup per
+ * problem, fp64, every sum in a fixed order: a problem's result does not depend on the other problems of the call.
+ *   dim [n]                 dimension of each prior, 1..SWF_FIX_PRIOR_MAXN (= 140: the largest matrix the root keeps in LDS; beyond: SWF_E_UNSUPPORTED)
+ *   J, r                    the priors' Jacobians (dim x dim row-major) and their residuals r = r0 + J dx(x, x0) at the NEW linearisation point,
+ *                           evaluated by the caller; concatenated over the problems (dim^2 / dim doubles each), as are all outputs
+ *   row_first [n + 1], rows [row_first[n]][2], vals [row_first[n]]   problem p owns rows row_first[p] .. row_first[p+1]-1; a row is
+ *                           (coordinate c of a one-dimensional kept block, group g) with value v: 0 for the group's reference ambiguity,
+ *                           the fixed integer for the others — both RELATIVE to the point the scalar is linearised at (the reference zeroes
+ *                           the ambiguities first, PhaseBiasSaveAndReset: there the values are the integers themselves).  Rows of one group
+ *                           share one hidden offset: a row is the residual istd ((x_c - tf_g) - v) of FixedIntegerFactor.
+ *   istd                    the weight of a row (the reference: 1 / 0.03);  eps, form: as swf_batch_marginalize
+ * With A0 = J^T J, b0 = J^T r, per group with members c_1 .. c_k:  A'[c_a, c_b] = A0[c_a, c_b] + istd^2 (delta_ab - 1 / k),
+ * b'[c_a] = b0[c_a] - istd^2 (v_a - mean(v)) — the Schur elimination of the offsets in closed form (they are mutually independent).
+ *   A, b                    A', b' (sign convention b = J^T r)
+ *   Jn, r0, eig, rank       the square root of (A', b'): SWF_PRIOR_EIGEN rows by ascending eigenvalue, eigenvalues <= eps dropped, rank = number
+ *                           kept, eigenvector signs not defined; SWF_PRIOR_CHOLESKY Jn = L^T upper triangular, r0 = L^-1 b', eig = diag(L)^2,
+ *                           rank = dim, or -1 (zeros) where A' is not positive definite
+ * Rejected (host memory: before the device is touched): a coordinate outside the prior, two rows of one problem on one coordinate, a group
+ * with a single row: SWF_E_INVALID.  on_device as for swf_lambda_batch; device-resident inputs cannot be checked by the host: a problem
+ * with a bad dimension or bad rows reports rank -1 and writes nothing else.  Only a problem whose dim is outside 1..140 counts as empty
+ * in the concatenation; one with bad rows still occupies its dim^2 / dim doubles.  Host memory: any output pointer may be NULL. */
+#define SWF_FIX_PRIOR_MAXN 140
+int swf_prior_fix_batch(int32_t n, const int32_t* dim, const double* J, const double* r, const int32_t* row_first, const int32_t* rows,
+                        const double* vals, double istd, double eps, int32_t form, double* A, double* b, double* Jn, double* r0,
+                        double* eig, int32_t* rank, int32_t on_device, void* stream);
 
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).
@@ -514,6 +580,17 @@ swf_factor_id swf_add_scalar_prior(swf_problem* p, double* scalar, double w);
  * problem), J dim x dim row-major, r0[dim], x0 = concatenated linearisation points. */
 swf_factor_id swf_add_linear_prior(swf_problem* p, double* const* keys, int32_t n_keys,
                                    const double* J, const double* r0, const double* x0);
+/* Fix and hold by key (the second half of LambdaSearch, R/swf/swf_lambda.cpp:254-343, for one window): prior_id = a swf_add_linear_prior
+ * factor; double difference i fixes *amb[i] - *ref[i] to N21[i] (the caller passes ROUND(F), as the reference does): one row (amb[i],
+ * group = ref[i], N21[i]) each and one row (ref, its group, 0) per distinct reference, through swf_prior_fix_batch with one problem.  The
+ * prior's residual is taken at the blocks' CURRENT values (read through the keys); scalars_at_zero != 0: one-dimensional kept blocks at 0
+ * (PhaseBiasSaveAndReset).  amb / ref must be one-dimensional blocks the prior keeps (SWF_E_INVALID); the operator's own rejections
+ * apply.  J [dim][dim], r0 [dim], x0 (global sizes, kept-block order): solver-owned, valid until the next swf_problem_fix_prior or
+ * destroy; any out pointer may be NULL.  The caller then does what the reference does at :344-354: swf_remove_factor(prior_id) and
+ * swf_add_linear_prior with the prior's own keys. */
+int swf_problem_fix_prior(swf_problem* p, swf_factor_id prior_id, double* const* amb, double* const* ref, const double* N21, int32_t n,
+                          int32_t scalars_at_zero, double istd, double eps, int32_t form, const double** J, const double** r0,
+                          const double** x0, int32_t* dim, int32_t* rank);
 int swf_remove_factor(swf_problem* p, swf_factor_id id);                  /* RemoveResidualBlock */
 int swf_factor_set_enabled(swf_problem* p, swf_factor_id id, int32_t on); /* ResidualBlock::is_use */
 int swf_factor_is_enabled(swf_problem* p, swf_factor_id id);              /* 1 / 0; SWF_E_NOTFOUND */

@@ -229,6 +229,17 @@ __device__ __forceinline__ void qinv(const double* q, double* o) {
     double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
     o[0] = -q[0] / n2; o[1] = -q[1] / n2; o[2] = -q[2] / n2; o[3] = q[3] / n2;
 }
+// dx of one kept block of a linear prior, as MarginalizationFactor::Evaluate forms it (R/factor/marginalization_factor.cpp:410-446);
+// gs = the block's global size (7 = pose: [p - p0 ; +-2 vec(q0^-1 q)], sign of the scalar part)
+__device__ __forceinline__ void prior_block_dx(const double* x, const double* x0, int gs, double* dx) {
+    if (gs != 7) { for (int k = 0; k < gs; k++) dx[k] = x[k] - x0[k]; return; }
+    dx[0] = x[0] - x0[0]; dx[1] = x[1] - x0[1]; dx[2] = x[2] - x0[2];
+    double q0i[4], dq[4];
+    qinv(x0 + 3, q0i);
+    qmul(q0i, x + 3, dq);
+    double sg = (dq[3] >= 0) ? 2.0 : -2.0;
+    dx[3] = sg * dq[0]; dx[4] = sg * dq[1]; dx[5] = sg * dq[2];
+}
 __device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
     o[0] = a[1] * b[2] - a[2] * b[1];
     o[1] = a[2] * b[0] - a[0] * b[2];

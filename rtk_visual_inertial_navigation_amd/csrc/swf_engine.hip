@@ -22,6 +22,7 @@
 #include "swf_kernels4.h"
 #include "swf_lambda.h"
 #include "swf_features.h"
+#include "swf_fixprior.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -29,7 +30,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 extern "C" const char* swf_last_error(void) { return g_err.c_str(); }
 void swf_internal_set_error(const std::string& m) { g_err = m; }
-extern "C" int swf_version(void) { return 108; }
+extern "C" int swf_version(void) { return 109; }
 extern "C" int swf_abi_sizes(int32_t out[5]) {
     if (!out) return fail(SWF_E_INVALID, "swf_abi_sizes: null");
     out[0] = (int32_t)sizeof(swf_options); out[1] = (int32_t)sizeof(swf_summary); out[2] = (int32_t)sizeof(swf_timing);
@@ -204,6 +205,9 @@ struct HostWin {       // what the host keeps per window for state transfer / ex
     int n_proj_all = 0;                                 // the caller's projection factors, fast path + generic path (GF_PROJX)
     std::vector<int> tail_x;                            // per tail coordinate: its state index if its block has size 1, else -1
     FeatWinSrc feat;                                    // the window's visual factors as the caller gave them (swf_batch_check_features builds its table from them)
+    // the window's linear priors (not the records of composite factors), in the caller's order, for swf_batch_fix_prior
+    struct LinPrior { int gf, dim, gsum; std::vector<int> col_x; };      // col_x: per prior column, the state index of its block if the block has size 1, else -1
+    std::vector<LinPrior> lin_prior;
 };
 
 struct swf_batch {
@@ -237,6 +241,13 @@ struct swf_batch {
     bool am_valid = false, am_host = false; std::vector<double> h_am;
     std::vector<int> am_nb;                             // pairs per window of the last search
     std::vector<int> am_h_first; std::vector<int4> am_h_pairs;      // host staging of the pair upload (outlives the asynchronous copy)
+    // fix and hold (swf_fixprior.h; allocated at the first swf_batch_fix_prior for the batch's largest linear prior): per-window table,
+    // tail-coordinate -> prior-column table, result slabs of fx_ldn^2 / fx_ldn / fx_ldx doubles per window, mirrored to the host by the first getter
+    FixWin* fx_win = nullptr; int* fx_tailcol = nullptr; double* fx_A = nullptr; double* fx_b = nullptr; double* fx_J = nullptr; double* fx_r0 = nullptr;
+    double* fx_eig = nullptr; double* fx_x0 = nullptr; int* fx_rank = nullptr; int* fx_applied = nullptr; int fx_ldn = 0, fx_ldx = 0;
+    bool fx_valid = false, fx_host = false; FixPriorArgs fx_args{};
+    std::vector<FixWin> fx_h_win; std::vector<int> fx_h_tailcol, fx_sel;
+    std::vector<double> h_fxA, h_fxb, h_fxJ, h_fxr0, h_fxeig, h_fxx0; std::vector<int> h_fxrank, h_fxapplied;
     // post-solve feature check (swf_features.h): the observation table and the output buffer are allocated at the first
     // swf_batch_check_features; fc_out = mean_err | depth | n_obs | rejected | n_rejected | flags, mirrored to the host by the first getter
     bool fc_built = false, fc_valid = false, fc_host = false; FeatArgs fc{}; char* fc_out = nullptr; size_t fc_bytes = 0; int fc_nfeat = 0;
@@ -620,6 +631,11 @@ int build_window(Build& B, const swf_flat_window* w, int wi, HostWin& hw) {
             int g = add_gf(GF_PRIOR, dim, data, blks);
             B.prior_gf.push_back(g);
             prior_first_gf.push_back(g);
+            {
+                HostWin::LinPrior lp{ g, dim, gsum, {} };
+                for (int b : blks) for (int q = 0; q < ls[b]; q++) lp.col_x.push_back(gs[b] == 1 ? gx(b) : -1);
+                hw.lin_prior.push_back(std::move(lp));
+            }
             B.max_prior_dim = std::max(B.max_prior_dim, dim);
             bo += nbk; jo += (long long)dim * dim; ro += dim; x0o += gsum;
         }
@@ -1902,7 +1918,7 @@ extern "C" int swf_batch_solve(swf_batch* b, const swf_options* opt) {
     b->last.lm_schur_flops = b->lm_schur_flops; b->last.n_obs = b->D.n_proj;
     b->last.lm_schur_flops_sym = b->lm_schur_flops_sym; b->last.lm_schur_mfma = b->lm_schur_mfma;
     b->last.n_linearizations = nlin;
-    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false; b->am_valid = false; b->fc_valid = false;      // consumer outputs belong to the previous solve
+    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false; b->am_valid = false; b->fx_valid = false; b->fc_valid = false;      // consumer outputs belong to the previous solve
     return SWF_OK;
 }
 
@@ -2242,7 +2258,7 @@ extern "C" int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_firs
     A.pair_first = b->am_first; A.pairs = b->am_pairs;
     A.tcQ = b->tc_Q; A.tc_ld = b->tc_ld; A.tc_n = b->tc_tail; A.tc_rank = b->tc_rank; A.x = b->D.x;
     A.rec = b->am_rec; A.rec_ld = LBD_REC_QB + nmax * nmax; A.thr = ratio_threshold;
-    b->am_valid = false;
+    b->am_valid = false; b->fx_valid = false;
     const int rc = swf_internal_lambda_launch(A, true, b->stream);
     if (rc) return rc;
     b->am_nb = nb; b->am_rec_ld = A.rec_ld;
@@ -2272,6 +2288,127 @@ extern "C" int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, d
     if (bf) memcpy(bf, r + LBD_REC_BF, n * sizeof(double));
     if (info) *info = (int32_t)r[LBD_REC_INFO];
     return SWF_OK;
+}
+
+// fix and hold: the accepted integers of the last search folded into a linear prior of every window (k_fix_prior<true>)
+extern "C" int swf_batch_fix_prior(swf_batch* b, const int32_t* prior_sel, const int32_t* n_use, const uint8_t* enable, int32_t ignore_ratio,
+                                   int32_t scalars_at_zero, double istd, double eps, int32_t form) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b) return fail(SWF_E_INVALID, "swf_batch_fix_prior: null batch");
+    if (!b->am_valid) return fail(SWF_E_STATE, "swf_batch_fix_prior needs a swf_batch_ambiguity_search after the last solve");
+    if (form != SWF_PRIOR_EIGEN && form != SWF_PRIOR_CHOLESKY) return fail(SWF_E_INVALID, "swf_batch_fix_prior: form must be SWF_PRIOR_EIGEN or SWF_PRIOR_CHOLESKY");
+    if (!std::isfinite(istd) || !(istd > 0.0) || !std::isfinite(eps) || eps < 0.0) return fail(SWF_E_INVALID, "swf_batch_fix_prior: istd must be positive and eps non-negative");
+    const int nw = (int)b->win.size();
+    // validated into locals and copied into the batch's staging on success: a refused call leaves the previous call's tables as they were
+    std::vector<FixWin> fw((size_t)nw, FixWin{ 0, 0, 0, 0 });
+    std::vector<int> tc;
+    std::vector<int> sel((size_t)nw, -1);
+    int cap_n = 1, cap_x = 1;
+    for (int w = 0; w < nw; w++) for (const HostWin::LinPrior& lp : b->hw[w].lin_prior) if (lp.dim <= FXP_MAXN) { cap_n = std::max(cap_n, lp.dim); cap_x = std::max(cap_x, lp.gsum); }
+    for (int w = 0; w < nw; w++) {
+        const HostWin& h = b->hw[w];
+        const int np_all = b->am_nb[w];
+        const int k = prior_sel ? prior_sel[w] : 0;
+        const bool en = !enable || enable[w];
+        int nu = n_use ? n_use[w] : np_all;
+        if (nu < 0) return fail(SWF_E_INVALID, "swf_batch_fix_prior: n_use < 0 (window " + std::to_string(w) + ")");
+        nu = std::min(nu, np_all);
+        fw[w].col0 = (int)tc.size(); fw[w].n_use = nu; fw[w].enable = (en && nu > 0) ? 1 : 0;
+        tc.resize(tc.size() + (size_t)h.tail_dim, -1);
+        if (!fw[w].enable) continue;             // nothing of this window is read
+        if (k < 0 || k >= (int)h.lin_prior.size())
+            return fail(SWF_E_INVALID, "swf_batch_fix_prior: prior_sel names no linear prior of the window (a composite factor's record cannot be fixed) (window " + std::to_string(w) + ")");
+        const HostWin::LinPrior& lp = h.lin_prior[(size_t)k];
+        if (lp.dim > FXP_MAXN) return fail(SWF_E_UNSUPPORTED, "swf_batch_fix_prior: prior of more than 140 dimensions (window " + std::to_string(w) + ")");
+        fw[w].gf = lp.gf; sel[w] = k;
+        int* tcw = tc.data() + fw[w].col0;
+        for (int t = 0; t < h.tail_dim; t++) if (h.tail_x[t] >= 0)
+            for (int c = 0; c < lp.dim; c++) if (lp.col_x[c] == h.tail_x[t]) { tcw[t] = c; break; }
+        // the rows this window will form: every coordinate kept by the prior, no coordinate twice, no group of one row
+        std::vector<int32_t> rows;
+        const int4* pr = b->am_h_pairs.data() + b->am_h_first[w];
+        for (int i = 0; i < nu; i++) {
+            bool first = true;
+            for (int j = 0; j < i; j++) if (pr[j].y == pr[i].y) { first = false; break; }
+            if (tcw[pr[i].x] < 0 || tcw[pr[i].y] < 0)
+                return fail(SWF_E_INVALID, "swf_batch_fix_prior: a pair names a tail coordinate whose block the prior does not keep (window " + std::to_string(w) + ")");
+            if (first) { rows.push_back(tcw[pr[i].y]); rows.push_back(pr[i].y); }
+            rows.push_back(tcw[pr[i].x]); rows.push_back(pr[i].y);
+        }
+        if ((int)rows.size() / 2 > lp.dim) return fail(SWF_E_INVALID, "swf_batch_fix_prior: more rows than coordinates (window " + std::to_string(w) + ")");
+        const int rc = swf_internal_fix_rows_check(lp.dim, (int)rows.size() / 2, rows.data(), "swf_batch_fix_prior");
+        if (rc) return rc;
+    }
+    if (!b->fx_win) {
+        int total_tail = 0;
+        for (int w = 0; w < nw; w++) total_tail += b->hw[w].tail_dim;
+        int rc = 0;
+        b->fx_ldn = cap_n; b->fx_ldx = cap_x;
+        rc |= b->pool.zeros((size_t)nw, &b->fx_win); rc |= b->pool.zeros((size_t)total_tail, &b->fx_tailcol);
+        rc |= b->pool.zeros((size_t)nw * cap_n * cap_n, &b->fx_A); rc |= b->pool.zeros((size_t)nw * cap_n * cap_n, &b->fx_J);
+        rc |= b->pool.zeros((size_t)nw * cap_n, &b->fx_b); rc |= b->pool.zeros((size_t)nw * cap_n, &b->fx_r0); rc |= b->pool.zeros((size_t)nw * cap_n, &b->fx_eig);
+        rc |= b->pool.zeros((size_t)nw * cap_x, &b->fx_x0); rc |= b->pool.zeros((size_t)nw, &b->fx_rank); rc |= b->pool.zeros((size_t)nw, &b->fx_applied);
+        if (rc) return fail(SWF_E_NODEVICE, "device allocation failed");
+    }
+    b->fx_valid = false;                         // from here on the device tables belong to this call
+    b->fx_h_win = fw; b->fx_h_tailcol = tc;      // (copied, not swapped: the staging keeps its storage from call to call, like am_h_pairs)
+    HIPCHK(hipMemcpyAsync(b->fx_win, b->fx_h_win.data(), (size_t)nw * sizeof(FixWin), hipMemcpyHostToDevice, b->stream));
+    if (!b->fx_h_tailcol.empty()) HIPCHK(hipMemcpyAsync(b->fx_tailcol, b->fx_h_tailcol.data(), b->fx_h_tailcol.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    FixPriorArgs P{};
+    P.n_prob = nw; P.form = form; P.istd = istd; P.eps = eps;
+    P.A = b->fx_A; P.b = b->fx_b; P.Jn = b->fx_J; P.r0 = b->fx_r0; P.eig = b->fx_eig; P.rank = b->fx_rank;
+    P.fw = b->fx_win; P.tailcol = b->fx_tailcol; P.pair_first = b->am_first; P.pairs = b->am_pairs; P.rec = b->am_rec; P.rec_ld = b->am_rec_ld;
+    P.ignore_ratio = ignore_ratio ? 1 : 0; P.scalars_at_zero = scalars_at_zero ? 1 : 0; P.ldn = b->fx_ldn; P.ldx = b->fx_ldx;
+    P.x0n = b->fx_x0; P.applied = b->fx_applied;
+    const int rc = swf_internal_fix_prior_launch(P, b->D, true, b->stream);
+    if (rc) return rc;
+    b->fx_args = P; b->fx_sel = sel;
+    b->fx_valid = true; b->fx_host = false;
+    return SWF_OK;
+}
+
+extern "C" int swf_batch_get_fixed_prior(swf_batch* b, int32_t w, double* A, double* bv, double* J, double* r0, double* x0, double* eig,
+                                         int32_t* n, int32_t* rank, int32_t* applied) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b || w < 0 || w >= (int)b->win.size()) return fail(SWF_E_INVALID, "bad window index");
+    if (!b->fx_valid) return fail(SWF_E_STATE, "swf_batch_get_fixed_prior before swf_batch_fix_prior (or after a new solve)");
+    if (!b->fx_host) {          // the first getter after a fix copies every window's results, one transfer per array
+        HIPCHK(hipStreamSynchronize(b->stream));
+        const size_t nw = b->win.size(), l1 = (size_t)b->fx_ldn, lx = (size_t)b->fx_ldx;
+        b->h_fxA.resize(nw * l1 * l1); b->h_fxJ.resize(nw * l1 * l1); b->h_fxb.resize(nw * l1); b->h_fxr0.resize(nw * l1); b->h_fxeig.resize(nw * l1);
+        b->h_fxx0.resize(nw * lx); b->h_fxrank.resize(nw); b->h_fxapplied.resize(nw);
+        HIPCHK(hipMemcpy(b->h_fxA.data(), b->fx_A, b->h_fxA.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->h_fxJ.data(), b->fx_J, b->h_fxJ.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->h_fxb.data(), b->fx_b, b->h_fxb.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->h_fxr0.data(), b->fx_r0, b->h_fxr0.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->h_fxeig.data(), b->fx_eig, b->h_fxeig.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->h_fxx0.data(), b->fx_x0, b->h_fxx0.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->h_fxrank.data(), b->fx_rank, nw * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->h_fxapplied.data(), b->fx_applied, nw * sizeof(int), hipMemcpyDeviceToHost));
+        b->fx_host = true;
+    }
+    const int ap = b->h_fxapplied[(size_t)w];
+    if (applied) *applied = ap;
+    if (rank) *rank = b->h_fxrank[(size_t)w];
+    const int k = b->fx_sel[(size_t)w];
+    const size_t dim = k >= 0 ? (size_t)b->hw[w].lin_prior[(size_t)k].dim : 0, gsum = k >= 0 ? (size_t)b->hw[w].lin_prior[(size_t)k].gsum : 0;
+    if (n) *n = (int32_t)dim;
+    if (!ap) return SWF_OK;                      // a window that was not applied has no results: nothing is written
+    const size_t l1 = (size_t)b->fx_ldn, o2 = (size_t)w * l1 * l1, o1 = (size_t)w * l1;
+    if (A) memcpy(A, b->h_fxA.data() + o2, dim * dim * sizeof(double));
+    if (J) memcpy(J, b->h_fxJ.data() + o2, dim * dim * sizeof(double));
+    if (bv) memcpy(bv, b->h_fxb.data() + o1, dim * sizeof(double));
+    if (r0) memcpy(r0, b->h_fxr0.data() + o1, dim * sizeof(double));
+    if (eig) memcpy(eig, b->h_fxeig.data() + o1, dim * sizeof(double));
+    if (x0) memcpy(x0, b->h_fxx0.data() + (size_t)w * b->fx_ldx, gsum * sizeof(double));
+    return SWF_OK;
+}
+
+extern "C" int swf_batch_install_fixed_prior(swf_batch* b) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b) return fail(SWF_E_INVALID, "swf_batch_install_fixed_prior: null batch");
+    if (!b->fx_valid) return fail(SWF_E_STATE, "swf_batch_install_fixed_prior before swf_batch_fix_prior (or after a new solve)");
+    return swf_internal_fix_install_launch(b->fx_args, b->D, b->stream);
 }
 
 // post-solve feature check (OutliersRejection + the depth sign of Double2Vector): k_feature_err, k_feature_compact

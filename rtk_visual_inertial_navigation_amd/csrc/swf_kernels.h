@@ -678,15 +678,7 @@ __global__ void __launch_bounds__(128) k_eval_idp(DevBatch B) {
 // r = r0 + J dx; the Jacobian is the constant J, so its J^T J (the prior clique's C) was
 // formed once at upload; per evaluation only r and J^T r are produced.  One workgroup/prior.
 // =========================================================================================
-__device__ __forceinline__ void prior_block_dx(const double* x, const double* x0, int gs, double* dx) {
-    if (gs != 7) { for (int k = 0; k < gs; k++) dx[k] = x[k] - x0[k]; return; }
-    dx[0] = x[0] - x0[0]; dx[1] = x[1] - x0[1]; dx[2] = x[2] - x0[2];
-    double q0i[4], dq[4];
-    qinv(x0 + 3, q0i);
-    qmul(q0i, x + 3, dq);
-    double sg = (dq[3] >= 0) ? 2.0 : -2.0;
-    dx[3] = sg * dq[0]; dx[4] = sg * dq[1]; dx[5] = sg * dq[2];
-}
+// (prior_block_dx, the dx of one kept block, lives in swf_dev.h: the fix-and-hold operator evaluates the prior with it too)
 #define PRIOR_LDS_DIM 512               // priors up to this dimension ride as a segment of the fused evaluation grids
 #define PRIOR_SPLIT_DIM 96              // priors beyond this dimension are evaluated in row chunks, a workgroup each
 #define PRIOR_CHUNK 32

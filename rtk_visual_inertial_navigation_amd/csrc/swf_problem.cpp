@@ -57,6 +57,7 @@ struct swf_problem {
     std::vector<double> S, rhs, L;
     std::vector<double> mgA, mgb, mgJ, mgr0;      // swf_problem_marginalize outputs
     std::vector<double> tcA, tcQ;                 // swf_problem_tail_covariance outputs
+    std::vector<double> fxJ, fxr0, fxx0;          // swf_problem_fix_prior outputs
     // swf_problem_check_features outputs: the features' keys (landmarks in pool order, then the inverse depths ascending) and rows
     bool fc_ok = false; std::vector<double*> fc_keys; std::unordered_map<const double*, int> fc_index;
     std::vector<double> fc_mean, fc_depth; std::vector<int32_t> fc_nobs, fc_rej; std::vector<uint8_t> fc_flags;
@@ -249,6 +250,63 @@ swf_factor_id swf_add_linear_prior(swf_problem* p, double* const* keys, int32_t 
     swf_factor_id id = add_factor(p, FT_PRIOR, k, sizes, data.data(), data.size());
     if (id >= 0) p->factors[id].dim = dim;
     return id;
+}
+// fix and hold for one window, blocks addressed by key (see include/swf_solver.h): the prior's residual at the blocks' current values
+// (host bookkeeping, swf_prior_reset_linearization_point), then the stand-alone device operator with one problem
+int swf_problem_fix_prior(swf_problem* p, swf_factor_id prior_id, double* const* amb, double* const* ref, const double* N21, int32_t n,
+                          int32_t scalars_at_zero, double istd, double eps, int32_t form, const double** J_out, const double** r0_out,
+                          const double** x0_out, int32_t* dim_out, int32_t* rank_out) {
+    if (!p || n < 1 || !amb || !ref || !N21) return pfail(SWF_E_INVALID, "swf_problem_fix_prior: bad arguments");
+    if (prior_id < 0 || prior_id >= (swf_factor_id)p->factors.size() || !p->factors[prior_id].alive || p->factors[prior_id].type != FT_PRIOR)
+        return pfail(SWF_E_INVALID, "swf_problem_fix_prior: prior_id is not a linear prior of this problem");
+    const PFactor& f = p->factors[prior_id];
+    const int dim = f.dim;
+    if (dim > SWF_FIX_PRIOR_MAXN) return pfail(SWF_E_UNSUPPORTED, "swf_problem_fix_prior: prior of more than 140 dimensions");
+    // kept blocks: sizes, first columns, current values
+    static const double zero = 0.0;
+    std::vector<int32_t> sizes; std::vector<const double*> xnew;
+    std::unordered_map<const double*, int> col_of;      // one-dimensional kept blocks only
+    int col = 0, gsum = 0;
+    for (double* k : f.keys) {
+        auto it = p->blocks.find(k);
+        if (it == p->blocks.end()) return pfail(SWF_E_NOTFOUND, "swf_problem_fix_prior: a kept block of the prior is not in the problem");
+        const int sz = it->second.size;
+        if (sz == 1) col_of[k] = col;
+        sizes.push_back(sz); xnew.push_back(sz == 1 && scalars_at_zero ? &zero : k);
+        col += sz == 7 ? 6 : sz; gsum += sz;
+    }
+    // rows: (column of amb[i], group = its reference, N21[i]); one (column of the reference, same group, 0) per distinct reference
+    std::vector<int32_t> rows; std::vector<double> vals;
+    std::unordered_map<const double*, int> group_of;
+    auto column = [&](const double* k) { auto it = col_of.find(k); return it == col_of.end() ? -1 : it->second; };
+    for (int i = 0; i < n; i++) {
+        const int ca = column(amb[i]), cb = column(ref[i]);
+        if (ca < 0 || cb < 0) return pfail(SWF_E_INVALID, "swf_problem_fix_prior: an ambiguity is not a one-dimensional block kept by the prior");
+        if (!group_of.count(ref[i])) {
+            const int g = (int)group_of.size();
+            group_of[ref[i]] = g;
+            rows.push_back(cb); rows.push_back(g); vals.push_back(0.0 - (scalars_at_zero ? 0.0 : *ref[i]));
+        }
+        // (a row's value is relative to the point its scalar is linearised at)
+        rows.push_back(ca); rows.push_back(group_of[ref[i]]); vals.push_back(N21[i] - (scalars_at_zero ? 0.0 : *amb[i]));
+    }
+    const double* data = f.data.data();
+    std::vector<double> r(data + (size_t)dim * dim, data + (size_t)dim * dim + dim);
+    p->fxx0.assign(data + (size_t)dim * dim + dim, data + (size_t)dim * dim + dim + gsum);
+    int rc = swf_prior_reset_linearization_point((int32_t)sizes.size(), sizes.data(), xnew.data(), dim, data, nullptr, r.data(), nullptr, p->fxx0.data());
+    if (rc) return rc;
+    p->fxJ.assign((size_t)dim * dim, 0.0); p->fxr0.assign((size_t)dim, 0.0);
+    const int32_t first[2] = { 0, (int32_t)vals.size() };
+    int32_t rank = 0;
+    rc = swf_prior_fix_batch(1, &dim, data, r.data(), first, rows.data(), vals.data(), istd, eps, form, nullptr, nullptr, p->fxJ.data(),
+                             p->fxr0.data(), nullptr, &rank, 0, nullptr);
+    if (rc) return rc;
+    if (J_out) *J_out = p->fxJ.data();
+    if (r0_out) *r0_out = p->fxr0.data();
+    if (x0_out) *x0_out = p->fxx0.data();
+    if (dim_out) *dim_out = dim;
+    if (rank_out) *rank_out = rank;
+    return SWF_OK;
 }
 int swf_remove_factor(swf_problem* p, swf_factor_id id) {
     if (!p || id < 0 || id >= (int)p->factors.size() || !p->factors[id].alive) return SWF_E_NOTFOUND;

@@ -58,6 +58,7 @@ EXPORTED = [
     "swf_lambda_batch", "swf_batch_ambiguity_search", "swf_batch_get_ambiguity_fix",
     "swf_batch_check_features", "swf_batch_get_feature_check",
     "swf_problem_check_features", "swf_problem_get_feature_check", "swf_problem_rejected_features",
+    "swf_prior_fix_batch", "swf_batch_fix_prior", "swf_batch_get_fixed_prior", "swf_batch_install_fixed_prior", "swf_problem_fix_prior",
 ]
 
 
@@ -232,6 +233,53 @@ class BatchSolver:
                  "swf_batch_get_ambiguity_fix")
             out.append(dict(F=F, s=sv, ratio=r, fixed=bool(fx.value), Qb=Qb, bf=bf, n_b=nb.value, info=info.value))
         return out
+
+    def fix_prior(self, prior_sel=None, n_use=None, enable=None, ignore_ratio=False, scalars_at_zero=True, istd=1.0 / 0.03, eps=1e-8, form=0):
+        """Fix and hold (the second half of LambdaSearch, R/swf/swf_lambda.cpp:249-355) for every window, on the device after
+        ambiguity_search(): the accepted integers of the search folded into linear prior prior_sel[w] (default 0) of each window.
+        n_use[w] = take the first n_use[w] pairs (default all), enable[w] = 0 leaves a window alone.  Asynchronous; read-only until
+        install_fixed_prior()."""
+        pi, pb = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        ps = None if prior_sel is None else np.ascontiguousarray(prior_sel, np.int32)
+        nu = None if n_use is None else np.ascontiguousarray(n_use, np.int32)
+        en = None if enable is None else np.ascontiguousarray(enable, np.uint8)
+        for a in (ps, nu, en):
+            if a is not None and a.size != self.n:
+                raise ValueError("fix_prior: one entry per window")
+        _chk(lib().swf_batch_fix_prior(self._h, None if ps is None else ps.ctypes.data_as(pi), None if nu is None else nu.ctypes.data_as(pi),
+                                       None if en is None else en.ctypes.data_as(pb), C.c_int32(1 if ignore_ratio else 0),
+                                       C.c_int32(1 if scalars_at_zero else 0), C.c_double(istd), C.c_double(eps), C.c_int32(form)),
+             "swf_batch_fix_prior")
+        self._fix_sel = np.zeros(self.n, np.int32) if ps is None else ps.copy()
+
+    def _prior_x0_size(self, w, k):
+        """Doubles of the linearisation point of linear prior k of window w (global sizes of its kept blocks)."""
+        win = self.windows[w]
+        nblk = np.asarray(win.a["prior_nblk"]).ravel()
+        b0 = int(nblk[:k].sum())
+        ids = np.asarray(win.a["prior_blk"]).ravel()[b0:b0 + int(nblk[k])]
+        return int(sum(7 if i < win.n_pose else 9 if i < win.n_pose + win.n_sb else 3 if i < win.n_pose + win.n_sb + win.n_lm else 1 for i in ids))
+
+    def get_fixed_prior(self, w=0):
+        """Results of fix_prior() for window w: dict(applied, rank, n, and — when applied — A, b, J, r0, x0, eig)."""
+        n, rank, ap = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _chk(lib().swf_batch_get_fixed_prior(self._h, C.c_int32(w), None, None, None, None, None, None, C.byref(n), C.byref(rank), C.byref(ap)),
+             "swf_batch_get_fixed_prior")
+        out = dict(applied=bool(ap.value), rank=rank.value, n=n.value)
+        if not ap.value:
+            return out
+        k = n.value
+        A, J, b, r0, eig, x0 = np.zeros((k, k)), np.zeros((k, k)), np.zeros(k), np.zeros(k), np.zeros(k), np.zeros(self._prior_x0_size(w, int(self._fix_sel[w])))
+        _chk(lib().swf_batch_get_fixed_prior(self._h, C.c_int32(w), A.ctypes.data_as(_pd), b.ctypes.data_as(_pd), J.ctypes.data_as(_pd),
+                                             r0.ctypes.data_as(_pd), x0.ctypes.data_as(_pd), eig.ctypes.data_as(_pd), C.byref(n), C.byref(rank),
+                                             C.byref(ap)), "swf_batch_get_fixed_prior")
+        out.update(A=A, b=b, J=J, r0=r0, eig=eig, x0=x0)
+        return out
+
+    def install_fixed_prior(self):
+        """Write (J', r0', x0') of every applied window into the batch's own prior record (and the clique data derived from it): the
+        next solve runs with the fix-and-hold prior, without a rebuild.  upload_state() / reset_state() do not undo it."""
+        _chk(lib().swf_batch_install_fixed_prior(self._h), "swf_batch_install_fixed_prior")
 
     def check_features(self, threshold=2.0):
         """The post-solve feature check of every window on the device (swf_batch_check_features: OutliersRejection's mean
@@ -525,6 +573,22 @@ class Problem:
             return dict(mean_err=m.value, depth=d.value, n_obs=no.value, flags=fl.value)
         return get, rejected
 
+    def FixPrior(self, fid, amb, ref, N21, scalars_at_zero=True, istd=1.0 / 0.03, eps=1e-8, form=0):
+        """Fix and hold for this problem (swf_problem_fix_prior): fold *amb[i] - *ref[i] = N21[i] into linear prior `fid`, evaluated at
+        the blocks' current values.  Returns dict(J, r0, x0, n, rank); then RemoveResidualBlock(fid) + AddLinearPrior(...) as the
+        reference does (R/swf/swf_lambda.cpp:344-354)."""
+        n = len(amb)
+        ka = (_pd * max(n, 1))(*[self._p(a) for a in amb]); kr = (_pd * max(n, 1))(*[self._p(a) for a in ref])
+        v = np.ascontiguousarray(N21, np.float64)
+        J, r0, x0, dim, rk = _pd(), _pd(), _pd(), C.c_int32(), C.c_int32()
+        _chk(lib().swf_problem_fix_prior(self._h, C.c_int32(fid), ka, kr, v.ctypes.data_as(_pd), C.c_int32(n), C.c_int32(1 if scalars_at_zero else 0),
+                                         C.c_double(istd), C.c_double(eps), C.c_int32(form), C.byref(J), C.byref(r0), C.byref(x0), C.byref(dim),
+                                         C.byref(rk)), "FixPrior")
+        d = dim.value
+        gs = sum(self.ParameterBlockSize(k) for k in self.GetParameterBlocksForResidualBlock(fid))
+        return dict(J=np.ctypeslib.as_array(J, (d, d)).copy(), r0=np.ctypeslib.as_array(r0, (d,)).copy(),
+                    x0=np.ctypeslib.as_array(x0, (gs,)).copy(), n=d, rank=rk.value)
+
     def GetReduced(self):
         S, r, L, n = _pd(), _pd(), _pd(), C.c_int32()
         _chk(lib().swf_get_reduced(self._h, C.byref(S), C.byref(r), C.byref(L), C.byref(n)), "GetReduced")
@@ -791,6 +855,40 @@ def lambda_batch(a_list, Q_list, m=2):
                                 C.c_int32(m), F.ctypes.data_as(_pd), s.ctypes.data_as(_pd), info.ctypes.data_as(pi), C.c_int32(0), None),
          "swf_lambda_batch")
     return [(F[p, :, :ns[p]].copy(), s[p].copy(), int(info[p])) for p in range(P)]
+
+
+FIX_PRIOR_MAXN = 140
+
+
+def prior_fix_batch(J_list, r_list, rows_list, istd=1.0 / 0.03, eps=1e-8, form=0):
+    """The stand-alone fix-and-hold operator (swf_prior_fix_batch) for a batch of linear priors: J_list[p] [n_p][n_p], r_list[p] [n_p]
+    (the prior's residual at the new linearisation point), rows_list[p] = [(coordinate, group, value), ...].  Returns one
+    dict(A, b, J, r0, eig, rank) per problem."""
+    P = len(J_list)
+    dims = np.array([np.asarray(r).size for r in r_list], np.int32)
+    first = np.zeros(P + 1, np.int32)
+    for p, rw in enumerate(rows_list):
+        first[p + 1] = first[p] + len(rw)
+    rows = np.ascontiguousarray(np.array([(c, g) for rw in rows_list for (c, g, _) in rw], np.int32).reshape(-1, 2)) if first[-1] else np.zeros((1, 2), np.int32)
+    vals = np.ascontiguousarray(np.array([v for rw in rows_list for (_, _, v) in rw], np.float64)) if first[-1] else np.zeros(1)
+    Jc = np.concatenate([np.asarray(J, np.float64).ravel() for J in J_list]) if P else np.zeros(1)
+    rc = np.concatenate([np.asarray(r, np.float64).ravel() for r in r_list]) if P else np.zeros(1)
+    t1, t2 = max(int(dims.sum()), 1), max(int((dims.astype(np.int64) ** 2).sum()), 1)
+    if Jc.size != (dims.astype(np.int64) ** 2).sum():
+        raise ValueError("prior_fix_batch: J must be dim x dim")
+    A, Jn, b, r0, eig, rank = np.zeros(t2), np.zeros(t2), np.zeros(t1), np.zeros(t1), np.zeros(t1), np.zeros(max(P, 1), np.int32)
+    pi = C.POINTER(C.c_int32)
+    _chk(lib().swf_prior_fix_batch(C.c_int32(P), dims.ctypes.data_as(pi), Jc.ctypes.data_as(_pd), rc.ctypes.data_as(_pd), first.ctypes.data_as(pi),
+                                   rows.ctypes.data_as(pi), vals.ctypes.data_as(_pd), C.c_double(istd), C.c_double(eps), C.c_int32(form),
+                                   A.ctypes.data_as(_pd), b.ctypes.data_as(_pd), Jn.ctypes.data_as(_pd), r0.ctypes.data_as(_pd),
+                                   eig.ctypes.data_as(_pd), rank.ctypes.data_as(pi), C.c_int32(0), None), "swf_prior_fix_batch")
+    out, o1, o2 = [], 0, 0
+    for p in range(P):
+        n = int(dims[p])
+        out.append(dict(A=A[o2:o2 + n * n].reshape(n, n).copy(), b=b[o1:o1 + n].copy(), J=Jn[o2:o2 + n * n].reshape(n, n).copy(),
+                        r0=r0[o1:o1 + n].copy(), eig=eig[o1:o1 + n].copy(), rank=int(rank[p])))
+        o1 += n; o2 += n * n
+    return out
 
 
 def problem_from_window(w):
