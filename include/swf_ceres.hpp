@@ -569,4 +569,82 @@ inline bool OutliersRejection(Problem& p, double threshold, std::vector<double*>
     return n == 0 || swf_problem_rejected_features(p.handle(), failed.data(), n, &n) == SWF_OK;
 }
 
+// The pre-fit carrier-phase screen: the first half of SWFOptimization::GnssPreprocess (R/swf/swf_gnss.cpp:337-499) for one epoch on
+// the device (swf_phase_screen_batch with one epoch; a caller that batches epochs builds the same records and makes one call).
+//   rover      the new epoch (the reference's mea_t*): obs_count, obs_data[i].{SVH, sys, el, satellite_pos, RTK_L, SPP_L, SPP_P,
+//              RTK_SLIP_COUNT, SPP_SLIP_COUNT, RTK_Npoint, SPP_Npoint}, Npoint->value, Npoint->SLIP_COUNT; read only
+//   pose       para_pose[g2f[ir]] (its first three entries);  base_xyz: rover->base_xyz;  lams[sys][f];  gnss_dt = para_gnss_dt[0]
+//   mode       SWF_SCR_GATE_RTK | SWF_SCR_GATE_SPP | SWF_SCR_RESET_ALL as the reference's conditions hold (:407, :417, :433)
+// One record per (observation, frequency, kind) that the reference evaluates or decides on: an observation with SVH set has none
+// (:347); a phase that is zero has one only if its Npoint exists (the reference still pushes that residual into the median, :354-362,
+// and decides nothing for it, :406 / :416): it is handed over as masked, which is exactly that.  The SPP record's partner is the
+// RTK record of the same observation and frequency (the reference's condition3, :454).  The reference also zeroes RTK_L / SPP_L /
+// SPP_P0 of an observation below the mask in place (:351-353): that write, like every PBtype the flags ask for, stays with the caller.
+// On success out->rtk / out->spp hold the flags (SWF_SCR_*) per observation and frequency, 0 where there is no record, the residuals
+// and the medians; new_rtk(i, f) / new_spp(i, f) say whether the reference would create a new ambiguity there.
+struct PhaseScreenResult {
+    int nfreq = 0;
+    std::vector<uint8_t> rtk, spp;               // [obs_count * nfreq] flags
+    std::vector<double> rtk_r, spp_r;            // [obs_count * nfreq] residuals (0 where there is no record)
+    double med[2][SWF_SCR_GROUPS];               // kind, group = sys * 2 + f
+    int32_t cnt[2][SWF_SCR_GROUPS];
+    std::vector<int32_t> reset;                  // the records with NEW_AMB, as (observation * nfreq + f) * 2 + kind, ascending by record
+    bool new_rtk(int i, int f) const { return (rtk[(size_t)i * nfreq + f] & SWF_SCR_NEW_AMB) != 0; }
+    bool new_spp(int i, int f) const { return (spp[(size_t)i * nfreq + f] & SWF_SCR_NEW_AMB) != 0; }
+};
+template <class Rover, class Lams>
+inline bool PhaseScreen(const Rover& rover, const double* pose, const double* base_xyz, const Lams& lams, const double* gnss_dt,
+                        int mode, double el_min, PhaseScreenResult* out, int nfreq = 2) {
+    if (!pose || !base_xyz || !gnss_dt || !out || nfreq < 1 || nfreq > 2 || rover.obs_count < 0) return false;
+    const int nobs = rover.obs_count;
+    const double below = -1e300;                             // an elevation under every mask
+    std::vector<double> dat;
+    std::vector<int32_t> rec, where;                         // where[record] = (observation * nfreq + f) * 2 + kind
+    for (int i = 0; i < nobs; i++) {
+        const auto& d = rover.obs_data[i];
+        if (d.SVH) continue;
+        const int sys = d.sys;
+        for (int f = 0; f < nfreq; f++) {
+            if (sys < 0 || sys * 2 + f >= SWF_SCR_GROUPS) return false;
+            const double lam = lams[sys][f];
+            int32_t partner = -1;
+            for (int kind = SWF_SCR_RTK; kind <= SWF_SCR_SPP; kind++) {
+                const bool rtk = kind == SWF_SCR_RTK;
+                const double L = rtk ? d.RTK_L[f] : d.SPP_L[f];
+                const auto* np_ = rtk ? d.RTK_Npoint[f] : d.SPP_Npoint[f];
+                if (L == 0 && !np_) continue;
+                const int slip = rtk ? d.RTK_SLIP_COUNT[f] : d.SPP_SLIP_COUNT[f];
+                const double row[SWF_SCR_DOUBLES] = { d.satellite_pos[0], d.satellite_pos[1], d.satellite_pos[2], L * lam, lam,
+                                                      L == 0 ? below : d.el, rtk ? 0.0 : d.SPP_P[f], np_ ? np_->value : 0.0,
+                                                      gnss_dt[rtk ? sys * 2 + f : 6 + sys * 2] };
+                dat.insert(dat.end(), row, row + SWF_SCR_DOUBLES);
+                const int32_t me = (int32_t)where.size();
+                const int32_t q[4] = { kind, sys * 2 + f, (np_ ? SWF_SCR_HAS_AMB : 0) | (np_ && np_->SLIP_COUNT == slip ? SWF_SCR_CONTINUING : 0),
+                                       rtk ? -1 : partner };
+                rec.insert(rec.end(), q, q + 4);
+                where.push_back((i * nfreq + f) * 2 + kind);
+                if (rtk) partner = me;
+            }
+        }
+    }
+    const int32_t n = (int32_t)where.size(), first[2] = { 0, n }, m = mode;
+    std::vector<double> r((size_t)n + 1);
+    std::vector<uint8_t> fl((size_t)n + 1);
+    std::vector<int32_t> rs((size_t)n + 1);
+    int32_t nr = 0;
+    dat.resize(dat.size() + SWF_SCR_DOUBLES); rec.resize(rec.size() + 4);          // (valid pointers for an epoch without records)
+    if (swf_phase_screen_batch(1, first, pose, base_xyz, &m, el_min, dat.data(), rec.data(), r.data(), fl.data(), &out->med[0][0],
+                               &out->cnt[0][0], rs.data(), &nr, 0, nullptr) != SWF_OK || nr < 0) return false;
+    out->nfreq = nfreq;
+    out->rtk.assign((size_t)nobs * nfreq, 0); out->spp.assign((size_t)nobs * nfreq, 0);
+    out->rtk_r.assign((size_t)nobs * nfreq, 0.0); out->spp_r.assign((size_t)nobs * nfreq, 0.0);
+    for (int32_t k = 0; k < n; k++) {
+        const size_t at = (size_t)(where[k] >> 1);
+        if (where[k] & 1) { out->spp[at] = fl[k]; out->spp_r[at] = r[k]; } else { out->rtk[at] = fl[k]; out->rtk_r[at] = r[k]; }
+    }
+    out->reset.clear();
+    for (int32_t k = 0; k < nr; k++) out->reset.push_back(where[rs[k]]);
+    return true;
+}
+
 }  // namespace swf_ceres

@@ -62,6 +62,8 @@ enum {
  * hidden offsets are eliminated in closed form, re-rooted), swf_batch_fix_prior / swf_batch_get_fixed_prior / swf_batch_install_fixed_prior
  * (the second half of LambdaSearch behind swf_batch_ambiguity_search, the new prior written into the resident batch without a rebuild),
  * swf_problem_fix_prior by parameter-block key.  A linear prior may keep blocks of the parameter_head tail.
+ * 110: no layout change; the pre-fit carrier-phase screen on the device: swf_phase_screen_batch (stand-alone: GnssPreprocess's residuals at
+ * the predicted pose, their medians per constellation and frequency, the slip flags and the compacted list of ambiguities to re-create).
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);
@@ -381,6 +383,54 @@ int swf_lambda_batch(int32_t n_problems, int32_t ld, const int32_t* n, const dou
 int swf_prior_fix_batch(int32_t n, const int32_t* dim, const double* J, const double* r, const int32_t* row_first, const int32_t* rows,
                         const double* vals, double istd, double eps, int32_t form, double* A, double* b, double* Jn, double* r0,
                         double* eig, int32_t* rank, int32_t on_device, void* stream);
+
+/* Pre-fit carrier-phase screen: the numeric core of the first half of SWFOptimization::GnssPreprocess (R/swf/swf_gnss.cpp:337-499)
+ * for a batch of epochs, one wavefront each.  A record is one carrier-phase observation of the new epoch: RTK (base-rover single
+ * difference) or SPP (rover-only phase).
+ *   first [n_epochs + 1]        epoch e owns records first[e] .. first[e+1]-1; an epoch without records is legal
+ *   pos, base [n_epochs][3]     the predicted position of the epoch's frame (para_pose[g2f[ir]][0..2]); the base-station position
+ *   mode [n_epochs]             SWF_SCR_GATE_RTK = USE_IMU && USE_RTK && solver_flag == NonLinear && rover_count > 1 (:407),
+ *                               SWF_SCR_GATE_SPP = the same with USE_SPP_PHASE (:417), SWF_SCR_RESET_ALL = not_fix_count > Phase_ALL_RESET_COUNT (:433)
+ *   el_min                      AZELMIN (the reference: 25 degrees, in radians)
+ *   dat [n][SWF_SCR_DOUBLES]    sat[3]; L_lam = the phase in metres; lam; el; P = the pseudorange of the code-minus-phase test (SPP only);
+ *                               N = the ambiguity's value; dt = the receiver clock (para_gnss_dt[0][sys*2+f] for RTK, [6+sys*2] for SPP)
+ *   rec [n][4]                  kind (SWF_SCR_RTK / _SPP); group sys * 2 + f in 0..5; state bits: SWF_SCR_HAS_AMB = the Npoint exists,
+ *                               SWF_SCR_CONTINUING = its SLIP_COUNT equals the observation's; partner = the index within the epoch of the
+ *                               RTK record of the same satellite and frequency, or -1 (read for SPP records only)
+ * Per epoch:
+ *   1. a record is MASKED iff el < el_min (:351-353); its L_lam is then taken as 0.
+ *   2. r = distance(pos + base, sat) - N lam - L_lam + dt, added left to right, for a record with HAS_AMB (:354-379: the un-weighted
+ *      RTKCarrierPhaseFactor, distance() with the Sagnac term); r = 0 without, and N, dt are then not used.
+ *   3. the median set of (kind, group) is the records with HAS_AMB && CONTINUING — masked ones included, as the reference pushes their
+ *      residual with the phase zeroed (:351-362).  cnt = its size; med = the element of rank cnt / 2 in ascending order (the upper median,
+ *      sorted[size / 2], :385), ties by record index, a NaN last; cnt = 0, med = NaN for an empty set.
+ *   4. un-masked records only (:402-472).  RTK: SLIP_RESIDUAL (the reference's condition3) iff GATE_RTK && HAS_AMB && CONTINUING &&
+ *      |r - med| > lam / 2;  NEW_AMB iff !HAS_AMB || !CONTINUING || SLIP_RESIDUAL || RESET_ALL.  SPP, under GATE_SPP && HAS_AMB && CONTINUING:
+ *      SLIP_CODE iff |(L_lam + N lam) - P| sin(el)^2 > 10, SLIP_RESIDUAL iff |r - med| > lam;  NEW_AMB iff !HAS_AMB || !CONTINUING ||
+ *      the partner's SLIP_RESIDUAL || SLIP_CODE || SLIP_RESIDUAL (RESET_ALL does not reach SPP records, :454).  A masked record carries
+ *      MASKED and nothing else; a comparison with a NaN sets no bit.
+ * Outputs: r [n], flags [n] (SWF_SCR_* output flags); med, cnt [n_epochs][2][SWF_SCR_GROUPS] indexed kind, then group; reset [n]: the
+ * within-epoch indices of the records with NEW_AMB, ascending, compacted on the device into reset[first[e] ..] (-1 behind them up to the
+ * epoch's end); n_reset [n_epochs].  An epoch's result does not depend on the other epochs of the call; every count runs in a fixed order.
+ * Rejected (host memory: before the device is touched): first[0] != 0 or a decreasing first, a kind, group or state bit out of range, a
+ * partner that is out of range, is the record itself or is not an RTK record, lam or el_min not finite, lam <= 0, null input pointers:
+ * SWF_E_INVALID; an epoch with more than SWF_SCR_NMAX records: SWF_E_UNSUPPORTED.  on_device as for swf_lambda_batch; device-resident
+ * inputs cannot be checked by the host: an epoch whose records the kernel finds invalid reports n_reset = -1 and writes nothing else.
+ * Any output pointer may be NULL.
+ * Stays with the caller: creating the PBtype entries the NEW_AMB flags ask for, continue_count, last_update_time and the 10 s staleness
+ * rule (:300-330, :434-495); the pseudorange-correction variables (:474-491); the seed mini-solve (:534-575, a small window the solver
+ * already expresses).  For a single epoch the host loop is faster than a launch: the operator is for batched epoch pipelines whose
+ * inputs and consumers (swf_batch_marginal_priors) are on the device. */
+#define SWF_SCR_NMAX 256           /* MAXOBS (64) x NFREQ (2) x {RTK, SPP} records per epoch */
+enum { SWF_SCR_RTK = 0, SWF_SCR_SPP = 1 };                                   /* kind */
+enum { SWF_SCR_HAS_AMB = 1, SWF_SCR_CONTINUING = 2 };                        /* record state bits */
+enum { SWF_SCR_GATE_RTK = 1, SWF_SCR_GATE_SPP = 2, SWF_SCR_RESET_ALL = 4 };  /* epoch mode bits */
+enum { SWF_SCR_MASKED = 1, SWF_SCR_SLIP_RESIDUAL = 2, SWF_SCR_SLIP_CODE = 4, SWF_SCR_NEW_AMB = 8 }; /* output flags */
+int swf_phase_screen_batch(int32_t n_epochs, const int32_t* first,
+                           const double* pos, const double* base, const int32_t* mode, double el_min,
+                           const double* dat, const int32_t* rec,
+                           double* r, uint8_t* flags, double* med, int32_t* cnt, int32_t* reset, int32_t* n_reset,
+                           int32_t on_device, void* stream);
 
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).

@@ -56,6 +56,10 @@ enum { SWF_SPR_DOUBLES = 5 };
 enum { SWF_SCP_DOUBLES = 6 };
 /* fixed-integer record doubles: N21 istd                      (FixedIntegerFactor, R/factor/gnss_factor.h:135-139) */
 enum { SWF_FIX_DOUBLES = 2 };
+/* pre-fit phase-screen record doubles (swf_phase_screen_batch): sat[3] L_lam lam el P N dt */
+enum { SWF_SCR_DOUBLES = 9 };
+/* (constellation, frequency) groups of the phase screen: sys * 2 + f, as the reference indexes median_error_*[6] (R/swf/swf_gnss.cpp:339) */
+enum { SWF_SCR_GROUPS = 6 };
 
 typedef struct swf_flat_window {
     /* ---- parameter pools: caller-owned; read at solve start, written back at solve end */

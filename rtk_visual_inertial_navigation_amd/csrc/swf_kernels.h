@@ -49,8 +49,7 @@ __device__ __forceinline__ double damp_diag(const DevOpt& O, double d, double* j
 template <bool JAC> __device__ __forceinline__ bool eval_gate(const DevBatch& B, const WinState& s) { return B.spec == 2 ? true : (JAC && !B.spec) ? s.need_lin != 0 : s.eval_cand != 0; }
 template <bool JAC> __device__ __forceinline__ const double* eval_src(const DevBatch& B) { return (JAC && !B.spec) ? B.x : B.xc; }
 
-#define CLIGHT_D 299792458.0
-#define OMGE_D 7.2921151467E-5
+#include "swf_gnss_range.h"          // CLIGHT_D, OMGE_D, gnss_distance (shared with the pre-fit phase screen)
 
 // =========================================================================================
 // projection_factor::Evaluate (R/factor/projection_factor.cpp:13-65) + CauchyLoss corrector
@@ -441,12 +440,6 @@ __global__ void __launch_bounds__(IMU_FPB * IMU_LPF) __attribute__((amdgpu_waves
 //   SppPseudorangeFactor   gnss_factor.cpp:9-39   SppCarrierPhaseFactor :45-80   FixedIntegerFactor :85-96
 //   distance() R/gnss/src/common_function.cpp:126-134 ; varerr2() gnss_factor.cpp:98-103 (sinf!)
 // =========================================================================================
-__device__ __forceinline__ double gnss_distance(const double* rr, const double* rs, double* e) {
-    e[0] = rr[0] - rs[0]; e[1] = rr[1] - rs[1]; e[2] = rr[2] - rs[2];
-    double r = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-    e[0] /= r; e[1] /= r; e[2] /= r;
-    return r + OMGE_D * (rs[0] * rr[1] - rs[1] * rr[0]) / CLIGHT_D;
-}
 __device__ __forceinline__ double varerr2(double el, double dt, double mea_var) {
     double b = CLIGHT_D * 5e-12 * dt;
     // the reference calls single-precision sinf() (gnss_factor.cpp:100).  glibc's sinf is

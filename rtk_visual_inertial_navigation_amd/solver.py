@@ -59,6 +59,7 @@ EXPORTED = [
     "swf_batch_check_features", "swf_batch_get_feature_check",
     "swf_problem_check_features", "swf_problem_get_feature_check", "swf_problem_rejected_features",
     "swf_prior_fix_batch", "swf_batch_fix_prior", "swf_batch_get_fixed_prior", "swf_batch_install_fixed_prior", "swf_problem_fix_prior",
+    "swf_phase_screen_batch",
 ]
 
 
@@ -888,6 +889,45 @@ def prior_fix_batch(J_list, r_list, rows_list, istd=1.0 / 0.03, eps=1e-8, form=0
         out.append(dict(A=A[o2:o2 + n * n].reshape(n, n).copy(), b=b[o1:o1 + n].copy(), J=Jn[o2:o2 + n * n].reshape(n, n).copy(),
                         r0=r0[o1:o1 + n].copy(), eig=eig[o1:o1 + n].copy(), rank=int(rank[p])))
         o1 += n; o2 += n * n
+    return out
+
+
+SCR_DOUBLES, SCR_GROUPS, SCR_NMAX = 9, 6, 256
+SCR_RTK, SCR_SPP = 0, 1
+SCR_HAS_AMB, SCR_CONTINUING = 1, 2
+SCR_GATE_RTK, SCR_GATE_SPP, SCR_RESET_ALL = 1, 2, 4
+SCR_MASKED, SCR_SLIP_RESIDUAL, SCR_SLIP_CODE, SCR_NEW_AMB = 1, 2, 4, 8
+AZELMIN = 25.0 * np.pi / 180.0
+
+
+def phase_screen_batch(first, pos, base, mode, dat, rec, el_min=AZELMIN):
+    """The pre-fit carrier-phase screen of GnssPreprocess (R/swf/swf_gnss.cpp:337-499) for a batch of epochs on the device
+    (swf_phase_screen_batch, which see): first [E + 1], pos / base [E][3], mode [E] (SCR_GATE_* | SCR_RESET_ALL), dat [n][9] =
+    sat[3] L_lam lam el P N dt, rec [n][4] = kind, group, state bits, partner.  Returns dict(r [n], flags [n], med [E][2][6],
+    cnt [E][2][6], reset [n] (an epoch's list starts at first[e], -1 behind it), n_reset [E])."""
+    first = np.ascontiguousarray(first, np.int32).ravel()
+    E = first.size - 1
+    if E < 0:
+        raise ValueError("phase_screen_batch: first needs n_epochs + 1 entries")
+    pos, base = (np.ascontiguousarray(v, np.float64).reshape(-1) for v in (pos, base))
+    mode = np.ascontiguousarray(mode, np.int32).ravel()
+    dat = np.ascontiguousarray(dat, np.float64).reshape(-1)
+    rec = np.ascontiguousarray(rec, np.int32).reshape(-1)
+    n = dat.size // SCR_DOUBLES
+    if pos.size != 3 * E or base.size != 3 * E or mode.size != E or dat.size != n * SCR_DOUBLES or rec.size != 4 * n or (E and int(first[-1]) > n):
+        raise ValueError("phase_screen_batch: array sizes do not match first")
+    pad = lambda a, k, t: a if a.size else np.zeros(k, t)              # (a valid pointer for an empty array)
+    pos, base, mode, dat, rec = pad(pos, 3, np.float64), pad(base, 3, np.float64), pad(mode, 1, np.int32), pad(dat, SCR_DOUBLES, np.float64), pad(rec, 4, np.int32)
+    out = dict(r=np.zeros(max(n, 1)), flags=np.zeros(max(n, 1), np.uint8), med=np.zeros((max(E, 1), 2, SCR_GROUPS)),
+               cnt=np.zeros((max(E, 1), 2, SCR_GROUPS), np.int32), reset=np.full(max(n, 1), -1, np.int32), n_reset=np.zeros(max(E, 1), np.int32))
+    pi = C.POINTER(C.c_int32)
+    _chk(lib().swf_phase_screen_batch(C.c_int32(E), first.ctypes.data_as(pi), pos.ctypes.data_as(_pd), base.ctypes.data_as(_pd),
+                                      mode.ctypes.data_as(pi), C.c_double(el_min), dat.ctypes.data_as(_pd), rec.ctypes.data_as(pi),
+                                      out["r"].ctypes.data_as(_pd), out["flags"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      out["med"].ctypes.data_as(_pd), out["cnt"].ctypes.data_as(pi), out["reset"].ctypes.data_as(pi),
+                                      out["n_reset"].ctypes.data_as(pi), C.c_int32(0), None), "swf_phase_screen_batch")
+    out["r"], out["flags"], out["reset"] = out["r"][:n], out["flags"][:n], out["reset"][:n]
+    out["med"], out["cnt"], out["n_reset"] = out["med"][:E], out["cnt"][:E], out["n_reset"][:E]
     return out
 
 
