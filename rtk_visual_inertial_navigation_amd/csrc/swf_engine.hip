@@ -1,17 +1,15 @@
 // swf_engine.hip — host side of the batch engine + the swf_batch_* C-ABI (include/swf_solver.h).
 //
-// Symbolic phase: flat windows -> index arrays (DevBatch), once per structure.
+// Symbolic phase: flat windows -> index arrays (DevBatch), once per structure: swf_plan.cpp, host-only; uploaded here.
 // Numeric phase: a fixed launch sequence per solve, no host synchronisation inside.
 // gfx950 only; there is no CPU path: without a HIP device every entry point fails loudly.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <memory>
 #include <thread>
@@ -23,6 +21,7 @@
 #include "swf_lambda.h"
 #include "swf_features.h"
 #include "swf_fixprior.h"
+#include "swf_plan.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -195,21 +194,6 @@ struct DevPool {
     }
 };
 
-struct HostWin {       // what the host keeps per window for state transfer / export
-    double *pose, *sb, *lm, *sc;
-    int n_pose, n_sb, n_lm, n_sc;
-    int tail_dim;
-    double *comp_pose = nullptr, *comp_sb = nullptr;    // hidden epochs of the window's composite factors (caller memory)
-    int comp_e0 = 0, comp_ne = 0;                       // their range in the batch-wide hidden-epoch arrays
-    std::vector<int> p_orig;                            // device observation (proj0 + q) -> the caller's projection factor index
-    int n_proj_all = 0;                                 // the caller's projection factors, fast path + generic path (GF_PROJX)
-    std::vector<int> tail_x;                            // per tail coordinate: its state index if its block has size 1, else -1
-    FeatWinSrc feat;                                    // the window's visual factors as the caller gave them (swf_batch_check_features builds its table from them)
-    // the window's linear priors (not the records of composite factors), in the caller's order, for swf_batch_fix_prior
-    struct LinPrior { int gf, dim, gsum; std::vector<int> col_x; };      // col_x: per prior column, the state index of its block if the block has size 1, else -1
-    std::vector<LinPrior> lin_prior;
-};
-
 struct swf_batch {
     int device = 0;                    // the HIP device the batch lives on (current at swf_batch_create)
     DevBatch D{};
@@ -282,1043 +266,121 @@ struct swf_batch {
     int last_mode = -1;
 };
 
-// ------------------------------------------------------------------ symbolic phase
-namespace {
-struct Build {
-    // concatenated host arrays
-    std::vector<WinRec> win;
-    std::vector<int> blk_xoff, blk_loc, blk_gs, loc2x;
-    std::vector<unsigned char> x_var;
-    std::vector<int> p_win, p_xpose, p_xex, p_xlm, p_lpose, p_llm, p_fr, p_lm;
-    std::vector<double> p_uv;
-    std::vector<int> lm_win, lm_obs0, lm_loc, lm_col;
-    std::vector<unsigned long long> lm_fmask;
-    std::vector<int> fsb_win, fsb_obs0, fsb_perm, fsb_foff, fsb_foff0, fsb_out0;
-    long long fs_tot = 0;
-    std::vector<int> fr_obs0, fr_obs, fr_red;
-    std::vector<GFac> gf;
-    std::vector<int> s_x, s_loc, s_ls, s_joff, s_ccol;
-    std::vector<double> imu_pre, cp_dat, pr_dat, dop_dat, sp_w, gx_dat;
-    std::vector<int> imu_gf, sc_gf, prior_gf, idp_gf;
-    std::vector<int> prior_dim, prior_roff, prior_x0off;
-    std::vector<long long> prior_Joff;
-    std::vector<double> prior_J, prior_r0, prior_x0;
-    std::vector<Clique> cl;
-    std::vector<int> cl_fac, cl_frow, cm_loc, cm_ls, cm_col;
-    std::vector<double> C_init, dgraw_init;      // static parts (prior cliques)
-    // composite factors (concatenated over the batch)
-    std::vector<int> co_M, co_N, co_gf, co_win, co_xo, co_xo_off{ 0 };
-    std::vector<double> co_pose, co_sb, co_pose_lin, co_sb_lin, co_Hpp, co_HpN, co_rhs_p, co_HNN, co_rhsN, co_pre, co_pbgw, co_H12;
-    std::vector<int> co_mid;
-    std::vector<Pair> pair;
-    std::vector<long long> pc_coff;
-    std::vector<int> pc_cld, pc_voff;
-    long long n_x = 0, n_loc = 0, S_tot = 0, Lt_tot = 0, P_tot = 0, C_tot = 0;
-    int v_tot = 0, e_tot = 0, r_tot = 0, j_tot = 0, n_fr = 0;
-    int max_tiles = 0, max_prior_dim = 0;
-    int64_t jac_bytes = 0;
-};
-
-int build_window(Build& B, const swf_flat_window* w, int wi, HostWin& hw) {
-    WinRec R{};
-    const int nP = w->n_pose, nS = w->n_sb, nL = w->n_lm, nC = w->n_sc;
-    const int nb = nP + nS + nL + nC;
-    if (nb <= 0) return fail(SWF_E_INVALID, "empty window");
-    hw = HostWin{ w->pose, w->sb, w->lm, w->sc, nP, nS, nL, nC, 0 };
-    R.x_base = (int)B.n_x; R.blk_base = (int)B.blk_xoff.size(); R.n_blk = nb;
-    R.loc_base = (int)B.n_loc;
-    std::vector<int> gs(nb), ls(nb), xo(nb), loc(nb, -1), grp(nb, -1);
-    int xoff = 0;
-    for (int b = 0; b < nb; b++) {
-        int g = b < nP ? 7 : b < nP + nS ? 9 : b < nP + nS + nL ? 3 : 1;
-        gs[b] = g; ls[b] = g == 7 ? 6 : g; xo[b] = xoff; xoff += g;
-    }
-    R.x_n = xoff;
-    int lo = 0, ne = 0, prevg = 0;
-    for (int i = 0; i < w->n_order; i++) {
-        int b = w->order_block[i], g = w->order_group[i];
-        if (b < 0 || b >= nb) return fail(SWF_E_INVALID, "ordering: block id out of range");
-        if (w->is_const[b]) return fail(SWF_E_INVALID, "ordering: constant block in ordering");
-        if (loc[b] >= 0) return fail(SWF_E_INVALID, "ordering: block listed twice");
-        if (g < prevg) return fail(SWF_E_INVALID, "ordering: groups must ascend");
-        prevg = g;
-        loc[b] = lo; grp[b] = g; lo += ls[b];
-        if (g == 0) ne += ls[b];
-    }
-    for (int b = 0; b < nb; b++) if (!w->is_const[b] && loc[b] < 0) return fail(SWF_E_INVALID, "ordering: variable block missing from ordering");
-    R.n_loc = lo; R.n_e = ne; R.n_red = lo - ne;
-    if (R.n_red + 1 > 1024) return fail(SWF_E_UNSUPPORTED, "reduced system larger than 1023");
-    R.S_base = B.S_tot; B.S_tot += (long long)(R.n_red + 1) * R.n_red;      // n x n (lower used) + the reduced rhs as row n
-    R.Lt_base = B.Lt_tot; B.Lt_tot += (long long)(R.n_red + 1) * (R.n_red + 1);
-    {
-        int td = 0;
-        hw.tail_x.clear();
-        for (int i = w->n_order - w->n_tail; i < w->n_order; i++) if (i >= 0) {
-            const int b = w->order_block[i];
-            td += ls[b];
-            for (int k = 0; k < ls[b]; k++) hw.tail_x.push_back(gs[b] == 1 ? R.x_base + xo[b] : -1);
-        }
-        hw.tail_dim = td; R.tail_dim = td;
-    }
-    if (nP > CTL_NT) return fail(SWF_E_UNSUPPORTED, "more than 256 pose blocks in a window");      // k_dogleg: a thread per pose block
-    R.n_pose_blk = nP;
-    B.loc2x.resize((size_t)R.loc_base + (size_t)R.n_loc, -1); B.x_var.resize((size_t)R.x_base + (size_t)R.x_n, 0);
-    for (int b = 0; b < nb; b++) {
-        B.blk_xoff.push_back(R.x_base + xo[b]);
-        B.blk_loc.push_back(loc[b] >= 0 ? R.loc_base + loc[b] : -1);
-        B.blk_gs.push_back(gs[b]);
-        if (loc[b] < 0) continue;
-        for (int k = 0; k < gs[b]; k++) B.x_var[(size_t)R.x_base + xo[b] + k] = 1;
-        if (gs[b] != 7) for (int k = 0; k < gs[b]; k++) B.loc2x[(size_t)R.loc_base + loc[b] + k] = R.x_base + xo[b] + k;
-    }
-    auto bidP = [&](int i) { return i; };
-    auto bidS = [&](int i) { return nP + i; };
-    auto bidL = [&](int i) { return nP + nS + i; };
-    auto bidC = [&](int i) { return nP + nS + nL + i; };
-    auto is_e = [&](int b) { return grp[b] == 0; };
-    auto gloc = [&](int b) { return loc[b] >= 0 ? R.loc_base + loc[b] : -1; };
-    auto gx = [&](int b) { return R.x_base + xo[b]; };
-
-    // ---- which landmarks leave the fast path (k_lm_schur: world point in group 0, constant extrinsic, one factor per frame)
-    // for the generic one (GF_PROJX factors in cliques): a variable extrinsic on any of its factors — the reference's
-    // marginalisation solves un-freeze para_ex_Pose (R/swf/swf_image.cpp:384-389) — or a variable landmark outside group 0
-    std::vector<char> lm_generic(nL, 0);
-    for (int i = 0; i < w->n_proj; i++) {
-        int p = w->proj_idx[i * 3], ex = w->proj_idx[i * 3 + 1], l = w->proj_idx[i * 3 + 2];
-        if (p < 0 || p >= nP || ex < 0 || ex >= nP || l < 0 || l >= nL) return fail(SWF_E_INVALID, "projection factor: index out of range");
-        if (loc[bidP(ex)] >= 0 || (loc[bidL(l)] >= 0 && !is_e(bidL(l)))) lm_generic[l] = 1;
-    }
-    hw.n_proj_all = w->n_proj;
-    {
-        FeatWinSrc& fs = hw.feat;
-        fs.x_base = R.x_base; fs.n_pose = nP; fs.n_sb = nS; fs.n_lm = nL; fs.n_sc = nC;
-        if (w->n_proj > 0) { fs.proj_idx.assign(w->proj_idx, w->proj_idx + (size_t)3 * w->n_proj); fs.proj_uv.assign(w->proj_uv, w->proj_uv + (size_t)2 * w->n_proj); }
-        if (w->n_idp > 0) {
-            fs.idp_kind.assign(w->idp_kind, w->idp_kind + w->n_idp); fs.idp_idx.assign(w->idp_idx, w->idp_idx + (size_t)5 * w->n_idp);
-            fs.idp_pts.assign(w->idp_pts, w->idp_pts + (size_t)6 * w->n_idp);
-        }
-        for (int k = 0; k < 3; k++) fs.pbg[k] = w->pbg[k];
-        fs.sqrt_info = w->proj_sqrt_info;
-    }
-    // ---- projection observations of the fast path sorted by (landmark, pose)
-    std::vector<int> ord;
-    for (int i = 0; i < w->n_proj; i++) if (!lm_generic[w->proj_idx[i * 3 + 2]]) ord.push_back(i);
-    const int n_fast = (int)ord.size();
-    // (sorted below, once the landmark records have their order)
-    // frames: variable, non-eliminated poses that carry observations, in pose order
-    std::vector<int> frame_of(nP, -1);
-    {
-        std::vector<char> seen(nP, 0);
-        for (int i : ord) seen[w->proj_idx[i * 3]] = 1;
-        int nf = 0;
-        for (int p = 0; p < nP; p++) if (seen[p] && loc[bidP(p)] >= 0) {
-            if (is_e(bidP(p))) return fail(SWF_E_UNSUPPORTED, "pose block in elimination group 0");
-            frame_of[p] = nf++;
-            B.fr_red.push_back(loc[bidP(p)] - ne);
-        }
-        R.nF = nf; R.fr_base = B.n_fr;
-    }
-    // Landmark records — and with them the observations — are laid out in the order k_lm_schur packs them into wave tasks: by the
-    // footprint of the track in the 16-row tiles of the reduced camera matrix (last tile, first tile), ties in the caller's order.
-    // A wave task's four landmarks then read four adjacent runs of every Jacobian array.  (Internal order only: the elimination
-    // order is that of the blocks, and hw.p_orig maps the observations back to the caller's factors.)
-    std::vector<int> lm_rank(nL), lm_perm(nL);
-    {
-        std::vector<unsigned> trs(nL, 0u);
-        for (int i : ord) {
-            int f = frame_of[w->proj_idx[i * 3]];
-            if (f >= 0 && f < 64) { trs[w->proj_idx[i * 3 + 2]] |= 1u << ((6 * f) / 16); trs[w->proj_idx[i * 3 + 2]] |= 1u << ((6 * f + 5) / 16); }
-        }
-        auto key = [&](int l) { unsigned t = trs[l]; return t ? (31 - __builtin_clz(t)) * 64 + __builtin_ctz(t) : (lm_generic[l] ? 1 << 20 : 0); };
-        for (int l = 0; l < nL; l++) lm_perm[l] = l;
-        std::stable_sort(lm_perm.begin(), lm_perm.end(), [&](int a, int b) { return key(a) < key(b); });
-        for (int r = 0; r < nL; r++) lm_rank[lm_perm[r]] = r;
-    }
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
-        int la = lm_rank[w->proj_idx[a * 3 + 2]], lb = lm_rank[w->proj_idx[b * 3 + 2]];
-        if (la != lb) return la < lb;
-        return w->proj_idx[a * 3] < w->proj_idx[b * 3];
-    });
-    R.proj0 = (int)B.p_win.size();
-    R.lm0 = (int)B.lm_win.size();
-    hw.p_orig = ord;
-    {
-        std::vector<std::vector<int>> fobs(R.nF);
-        std::vector<int> lm_first(nL + 1, 0);
-        for (int q = 0; q < n_fast; q++) {
-            int i = ord[q];
-            int p = w->proj_idx[i * 3], ex = w->proj_idx[i * 3 + 1], l = w->proj_idx[i * 3 + 2];
-            if (q > 0 && w->proj_idx[ord[q - 1] * 3 + 2] == l && w->proj_idx[ord[q - 1] * 3] == p && frame_of[p] >= 0)
-                return fail(SWF_E_UNSUPPORTED, "two projection factors of one landmark in the same frame");
-            int gi = (int)B.p_win.size();
-            B.p_win.push_back(wi);
-            B.p_xpose.push_back(gx(bidP(p))); B.p_xex.push_back(gx(bidP(ex))); B.p_xlm.push_back(gx(bidL(l)));
-            B.p_lpose.push_back(gloc(bidP(p))); B.p_llm.push_back(gloc(bidL(l)));
-            B.p_fr.push_back(frame_of[p]); B.p_lm.push_back(R.lm0 + lm_rank[l]);
-            B.p_uv.push_back(w->proj_uv[i * 2]); B.p_uv.push_back(w->proj_uv[i * 2 + 1]);
-            if (frame_of[p] >= 0) fobs[frame_of[p]].push_back(gi);
-            lm_first[lm_rank[l] + 1]++;
-        }
-        for (int l = 0; l < nL; l++) lm_first[l + 1] += lm_first[l];
-        for (int rk = 0; rk < nL; rk++) {
-            const int l = lm_perm[rk];
-            int b = bidL(l);
-            B.lm_win.push_back(wi);
-            B.lm_obs0.push_back(R.proj0 + lm_first[rk]);
-            B.lm_loc.push_back(lm_generic[l] ? -1 : gloc(b));        // a generic-path landmark has no observations here: an inactive record
-            B.lm_col.push_back(3 * l);
-            B.lm_fmask.push_back(0ULL);
-        }
-        for (int q = R.proj0; q < (int)B.p_win.size(); q++) {
-            int f = B.p_fr[q];
-            if (f >= 0) B.lm_fmask[B.p_lm[q]] |= (f < 64) ? (1ULL << f) : ~0ULL;
-        }
-        if (R.nF > 64) for (int l = 0; l < nL; l++) B.lm_fmask[R.lm0 + l] = ~0ULL;   // no skipping beyond 64 frames
-        for (int f = 0; f < R.nF; f++) {
-            B.fr_obs0.push_back((int)B.fr_obs.size());
-            for (int o : fobs[f]) B.fr_obs.push_back(o);
-        }
-        B.n_fr += R.nF;
-    }
-    R.proj1 = (int)B.p_win.size();
-    R.lm1 = (int)B.lm_win.size();
-    // frame-sum blocks: <= FS_BLK consecutive observations, frame-sorted permutation per block
-    R.fsb0 = (int)B.fsb_win.size();
-    for (int o0 = R.proj0; o0 < R.proj1; o0 += FS_BLK) {
-        int cnt = std::min(FS_BLK, R.proj1 - o0);
-        B.fsb_win.push_back(wi); B.fsb_obs0.push_back(o0);
-        B.fsb_foff0.push_back((int)B.fsb_foff.size());
-        B.fsb_out0.push_back((int)B.fs_tot); B.fs_tot += R.nF;
-        std::vector<std::vector<int>> byf(R.nF);
-        for (int t = 0; t < cnt; t++) { int f = B.p_fr[o0 + t]; if (f >= 0) byf[f].push_back(t); }
-        // fsb_perm[o] = rank of observation o in the block's frame-sorted order (observations of constant poses go last)
-        int pos = 0;
-        B.fsb_perm.resize((size_t)o0 + cnt, -1);
-        for (int f = 0; f < R.nF; f++) {
-            B.fsb_foff.push_back(pos);
-            for (int t : byf[f]) B.fsb_perm[(size_t)o0 + t] = pos++;
-        }
-        B.fsb_foff.push_back(pos);
-        for (int t = 0; t < cnt; t++) if (B.fsb_perm[(size_t)o0 + t] < 0) B.fsb_perm[(size_t)o0 + t] = pos++;
-    }
-    R.fsb1 = (int)B.fsb_win.size();
-    R.P_base = B.P_tot; B.P_tot += (long long)36 * R.nF * R.nF;       // x GEMM_SPLIT partial products at allocation
-    {
-        int m = 6 * R.nF, nt = (m + 15) / 16;
-        B.max_tiles = std::max(B.max_tiles, nt * (nt + 1) / 2);
-        if (R.nF > LS_MAXF) return fail(SWF_E_UNSUPPORTED, "more than 64 observing frames in one window");
-    }
-
-    // ---- generic factors
-    R.gf0 = (int)B.gf.size();
-    struct TmpF { std::vector<int> blk; };
-    std::vector<TmpF> tf;
-    auto add_gf = [&](int type, int nres, int data, const std::vector<int>& blks) {
-        GFac G{};
-        G.type = type; G.win = wi; G.nres = nres; G.nslot = (int)blks.size();
-        G.slot0 = (int)B.s_x.size(); G.roff = -1; G.data = data; G.clique = -1;
-        for (int b : blks) {
-            B.s_x.push_back(gx(b)); B.s_loc.push_back(gloc(b)); B.s_ls.push_back(ls[b]);
-            // Jacobian block placement (s_joff, s_jld) and the residual offset are assigned with the cliques below
-            B.s_joff.push_back((loc[b] >= 0 && type != GF_PRIOR) ? 0 : -1);
-            B.s_ccol.push_back(-1);
-        }
-        B.gf.push_back(G);
-        tf.push_back(TmpF{ blks });
-        return (int)B.gf.size() - 1;
-    };
-#define CHK(i, n, what) if ((i) < 0 || (i) >= (n)) return fail(SWF_E_INVALID, what ": index out of range");
-    for (int i = 0; i < w->n_imu; i++) {
-        const int* ix = w->imu_idx + i * 4;
-        CHK(ix[0], nP, "imu") CHK(ix[1], nS, "imu") CHK(ix[2], nP, "imu") CHK(ix[3], nS, "imu")
-        int data = (int)(B.imu_pre.size() / SWF_PRE_DOUBLES);
-        B.imu_pre.insert(B.imu_pre.end(), w->imu_pre + (size_t)i * SWF_PRE_DOUBLES, w->imu_pre + (size_t)(i + 1) * SWF_PRE_DOUBLES);
-        B.imu_gf.push_back(add_gf(GF_IMU, 15, data, { bidP(ix[0]), bidS(ix[1]), bidP(ix[2]), bidS(ix[3]) }));
-    }
-    for (int i = 0; i < w->n_cp; i++) {
-        const int* ix = w->cp_idx + i * 3;
-        CHK(ix[0], nP, "carrier phase") CHK(ix[1], nC, "carrier phase") CHK(ix[2], nC, "carrier phase")
-        int data = (int)(B.cp_dat.size() / SWF_CP_DOUBLES);
-        B.cp_dat.insert(B.cp_dat.end(), w->cp_dat + i * SWF_CP_DOUBLES, w->cp_dat + (i + 1) * SWF_CP_DOUBLES);
-        B.sc_gf.push_back(add_gf(GF_CP, 1, data, { bidP(ix[0]), bidC(ix[1]), bidC(ix[2]) }));
-    }
-    for (int i = 0; i < w->n_pr; i++) {
-        const int* ix = w->pr_idx + i * 2;
-        CHK(ix[0], nP, "pseudorange") CHK(ix[1], nC, "pseudorange")
-        int data = (int)(B.pr_dat.size() / SWF_PR_DOUBLES);
-        B.pr_dat.insert(B.pr_dat.end(), w->pr_dat + i * SWF_PR_DOUBLES, w->pr_dat + (i + 1) * SWF_PR_DOUBLES);
-        B.sc_gf.push_back(add_gf(GF_PR, 1, data, { bidP(ix[0]), bidC(ix[1]) }));
-    }
-    for (int i = 0; i < w->n_dop; i++) {
-        const int* ix = w->dop_idx + i * 3;
-        CHK(ix[0], nS, "doppler") CHK(ix[1], nC, "doppler") CHK(ix[2], nP, "doppler")
-        int data = (int)(B.dop_dat.size() / SWF_DOP_DOUBLES);
-        B.dop_dat.insert(B.dop_dat.end(), w->dop_dat + i * SWF_DOP_DOUBLES, w->dop_dat + (i + 1) * SWF_DOP_DOUBLES);
-        B.sc_gf.push_back(add_gf(GF_DOP, 1, data, { bidS(ix[0]), bidC(ix[1]), bidP(ix[2]) }));
-    }
-    for (int i = 0; i < w->n_sp; i++) {
-        CHK(w->sp_idx[i], nC, "scalar prior")
-        int data = (int)B.sp_w.size();
-        B.sp_w.push_back(w->sp_w[i]);
-        B.sc_gf.push_back(add_gf(GF_SP, 1, data, { bidC(w->sp_idx[i]) }));
-    }
-    // rover-only pseudorange / carrier phase and fixed-integer factors share one record pool (GFac.data = offset in doubles)
-    for (int i = 0; i < w->n_spr; i++) {
-        const int* ix = w->spr_idx + i * 2;
-        CHK(ix[0], nP, "spp pseudorange") CHK(ix[1], nC, "spp pseudorange")
-        int data = (int)B.gx_dat.size();
-        B.gx_dat.insert(B.gx_dat.end(), w->spr_dat + i * SWF_SPR_DOUBLES, w->spr_dat + (i + 1) * SWF_SPR_DOUBLES);
-        B.sc_gf.push_back(add_gf(GF_SPR, 1, data, { bidP(ix[0]), bidC(ix[1]) }));
-    }
-    for (int i = 0; i < w->n_scp; i++) {
-        const int* ix = w->scp_idx + i * 3;
-        CHK(ix[0], nP, "spp carrier phase") CHK(ix[1], nC, "spp carrier phase") CHK(ix[2], nC, "spp carrier phase")
-        int data = (int)B.gx_dat.size();
-        B.gx_dat.insert(B.gx_dat.end(), w->scp_dat + i * SWF_SCP_DOUBLES, w->scp_dat + (i + 1) * SWF_SCP_DOUBLES);
-        B.sc_gf.push_back(add_gf(GF_SCP, 1, data, { bidP(ix[0]), bidC(ix[1]), bidC(ix[2]) }));
-    }
-    for (int i = 0; i < w->n_fix; i++) {
-        const int* ix = w->fix_idx + i * 2;
-        CHK(ix[0], nC, "fixed integer") CHK(ix[1], nC, "fixed integer")
-        if (ix[0] == ix[1]) return fail(SWF_E_INVALID, "fixed integer: both blocks are the same scalar");
-        int data = (int)B.gx_dat.size();
-        B.gx_dat.insert(B.gx_dat.end(), w->fix_dat + i * SWF_FIX_DOUBLES, w->fix_dat + (i + 1) * SWF_FIX_DOUBLES);
-        B.sc_gf.push_back(add_gf(GF_FIX, 1, data, { bidC(ix[0]), bidC(ix[1]) }));
-    }
-    // inverse-depth projection factors: two residual rows, evaluated one lane each with the scalar factors; record = kind | pts (6)
-    for (int i = 0; i < w->n_idp; i++) {
-        const int* ix = w->idp_idx + i * 5; const int kd = w->idp_kind[i];
-        if (kd < 0 || kd > 2) return fail(SWF_E_INVALID, "inverse-depth projection: kind must be 0, 1 or 2");
-        std::vector<int> blks;
-        if (kd != 2) { CHK(ix[0], nP, "inverse-depth projection") CHK(ix[1], nP, "inverse-depth projection") blks.push_back(bidP(ix[0])); blks.push_back(bidP(ix[1])); }
-        CHK(ix[2], nP, "inverse-depth projection") blks.push_back(bidP(ix[2]));
-        if (kd != 0) { CHK(ix[3], nP, "inverse-depth projection") blks.push_back(bidP(ix[3])); }
-        CHK(ix[4], nC, "inverse-depth projection") blks.push_back(bidC(ix[4]));
-        for (size_t a = 0; a < blks.size(); a++) for (size_t c2 = 0; c2 < a; c2++)
-            if (blks[a] == blks[c2]) return fail(SWF_E_INVALID, "inverse-depth projection: repeated parameter block");
-        int data = (int)B.gx_dat.size();
-        B.gx_dat.push_back((double)kd);
-        B.gx_dat.insert(B.gx_dat.end(), w->idp_pts + (size_t)i * 6, w->idp_pts + (size_t)(i + 1) * 6);
-        { int g = add_gf(GF_IDP, 2, data, blks); B.sc_gf.push_back(g); B.idp_gf.push_back(g); }
-    }
-    // world-point projection factors of the generic path (GF_PROJX): record = uv; GFac.pad = the caller's factor index
-    for (int i = 0; i < w->n_proj; i++) {
-        const int* ix = w->proj_idx + i * 3;
-        if (!lm_generic[ix[2]]) continue;
-        int data = (int)B.gx_dat.size();
-        B.gx_dat.push_back(w->proj_uv[i * 2]); B.gx_dat.push_back(w->proj_uv[i * 2 + 1]);
-        int g = add_gf(GF_PROJX, 2, data, { bidP(ix[0]), bidP(ix[1]), bidL(ix[2]) });
-        B.gf[g].pad = i;
-        B.sc_gf.push_back(g); B.idp_gf.push_back(g);
-    }
-    std::vector<int> prior_first_gf;
-    {
-        int bo = 0; long long jo = 0; int ro = 0, x0o = 0;
-        for (int k = 0; k < w->n_prior; k++) {
-            int nbk = w->prior_nblk[k], dim = w->prior_dim[k];
-            std::vector<int> blks(w->prior_blk + bo, w->prior_blk + bo + nbk);
-            int dsum = 0, gsum = 0;
-            for (int b : blks) { CHK(b, nb, "prior") dsum += ls[b]; gsum += gs[b]; }
-            if (dsum != dim) return fail(SWF_E_INVALID, "prior: dim != sum of local block sizes");
-            int data = (int)B.prior_dim.size();
-            B.prior_dim.push_back(dim);
-            B.prior_Joff.push_back((long long)B.prior_J.size());
-            B.prior_roff.push_back((int)B.prior_r0.size());
-            B.prior_x0off.push_back((int)B.prior_x0.size());
-            B.prior_J.insert(B.prior_J.end(), w->prior_J + jo, w->prior_J + jo + (long long)dim * dim);
-            B.prior_r0.insert(B.prior_r0.end(), w->prior_r0 + ro, w->prior_r0 + ro + dim);
-            B.prior_x0.insert(B.prior_x0.end(), w->prior_x0 + x0o, w->prior_x0 + x0o + gsum);
-            int g = add_gf(GF_PRIOR, dim, data, blks);
-            B.prior_gf.push_back(g);
-            prior_first_gf.push_back(g);
-            {
-                HostWin::LinPrior lp{ g, dim, gsum, {} };
-                for (int b : blks) for (int q = 0; q < ls[b]; q++) lp.col_x.push_back(gs[b] == 1 ? gx(b) : -1);
-                hw.lin_prior.push_back(std::move(lp));
-            }
-            B.max_prior_dim = std::max(B.max_prior_dim, dim);
-            bo += nbk; jo += (long long)dim * dim; ro += dim; x0o += gsum;
-        }
-    }
-    // composite IMU-GNSS factors: carried as prior-type factors whose record k_comp_scatter rewrites at every linearisation
-    hw.comp_pose = w->comp_pose; hw.comp_sb = w->comp_sb; hw.comp_e0 = (int)(B.co_pose.size() / 7);
-    {
-        int io = 0; long long pn = 0, nn = 0; int no = 0, e0 = 0;
-        for (int k = 0; k < w->n_comp; k++) {
-            const int M = w->comp_M[k], N = w->comp_N[k], G = 30 + N;
-            if (M < 1) return fail(SWF_E_INVALID, "composite factor without hidden epochs");
-            if (N < 0 || N > CO_MAXN) return fail(SWF_E_UNSUPPORTED, "composite factor with more than 64 ambiguities");
-            const int* ix = w->comp_idx + io;
-            CHK(ix[0], nP, "composite") CHK(ix[1], nS, "composite") CHK(ix[2], nP, "composite") CHK(ix[3], nS, "composite")
-            std::vector<int> blks = { bidP(ix[0]), bidS(ix[1]), bidP(ix[2]), bidS(ix[3]) };
-            for (int q = 0; q < N; q++) { CHK(ix[4 + q], nC, "composite") blks.push_back(bidC(ix[4 + q])); }
-            for (size_t a = 0; a < blks.size(); a++) {
-                if (loc[blks[a]] < 0) return fail(SWF_E_UNSUPPORTED, "composite factor on a constant parameter block");
-                for (size_t c2 = 0; c2 < a; c2++) if (blks[c2] == blks[a]) return fail(SWF_E_INVALID, "composite factor: repeated parameter block");
-            }
-            int data = (int)B.prior_dim.size();
-            B.prior_dim.push_back(G);
-            B.prior_Joff.push_back((long long)B.prior_J.size()); B.prior_roff.push_back((int)B.prior_r0.size()); B.prior_x0off.push_back((int)B.prior_x0.size());
-            B.prior_J.resize(B.prior_J.size() + (size_t)G * G, 0.0); B.prior_r0.resize(B.prior_r0.size() + G, 0.0);
-            {   // a valid linearisation point until the first k_comp_scatter: the blocks' current values
-                const double* src[4] = { w->pose + 7 * ix[0], w->sb + 9 * ix[1], w->pose + 7 * ix[2], w->sb + 9 * ix[3] };
-                const int gsz[4] = { 7, 9, 7, 9 };
-                for (int a = 0; a < 4; a++) B.prior_x0.insert(B.prior_x0.end(), src[a], src[a] + gsz[a]);
-                for (int q = 0; q < N; q++) B.prior_x0.push_back(w->sc[ix[4 + q]]);
-            }
-            int g = add_gf(GF_PRIOR, G, data, blks);
-            B.prior_gf.push_back(g);
-            B.max_prior_dim = std::max(B.max_prior_dim, G);
-            B.co_M.push_back(M); B.co_N.push_back(N); B.co_gf.push_back(g); B.co_win.push_back(wi);
-            for (int b : blks) B.co_xo.push_back(gx(b));
-            B.co_xo_off.push_back((int)B.co_xo.size());
-            B.co_pose.insert(B.co_pose.end(), w->comp_pose + (size_t)e0 * 7, w->comp_pose + (size_t)(e0 + M) * 7);
-            B.co_sb.insert(B.co_sb.end(), w->comp_sb + (size_t)e0 * 9, w->comp_sb + (size_t)(e0 + M) * 9);
-            B.co_pose_lin.insert(B.co_pose_lin.end(), w->comp_pose_lin + (size_t)e0 * 7, w->comp_pose_lin + (size_t)(e0 + M) * 7);
-            B.co_sb_lin.insert(B.co_sb_lin.end(), w->comp_sb_lin + (size_t)e0 * 9, w->comp_sb_lin + (size_t)(e0 + M) * 9);
-            B.co_Hpp.insert(B.co_Hpp.end(), w->comp_Hpp + (size_t)e0 * 225, w->comp_Hpp + (size_t)(e0 + M) * 225);
-            B.co_HpN.insert(B.co_HpN.end(), w->comp_HpN + pn, w->comp_HpN + pn + 15LL * M * N);
-            B.co_rhs_p.insert(B.co_rhs_p.end(), w->comp_rhs_p + (size_t)e0 * 15, w->comp_rhs_p + (size_t)(e0 + M) * 15);
-            B.co_HNN.insert(B.co_HNN.end(), w->comp_HNN + nn, w->comp_HNN + nn + (long long)N * N);
-            B.co_rhsN.insert(B.co_rhsN.end(), w->comp_rhsN + no, w->comp_rhsN + no + N);
-            B.co_pre.insert(B.co_pre.end(), w->comp_pre + (size_t)(e0 + k) * SWF_PRE_DOUBLES, w->comp_pre + (size_t)(e0 + k + M + 1) * SWF_PRE_DOUBLES);
-            {   // middle-marginalisation link (AddMidMargInfo): optional
-                int mid = w->comp_mid ? w->comp_mid[k] : 0;
-                if (mid != 0 && (mid < 1 || mid > M - 1 || !w->comp_H12)) return fail(SWF_E_INVALID, "composite factor: comp_mid must be 0 or a link between two hidden epochs (1..M-1), with comp_H12 given");
-                B.co_mid.push_back(mid);
-                if (mid) B.co_H12.insert(B.co_H12.end(), w->comp_H12 + (size_t)k * 225, w->comp_H12 + (size_t)(k + 1) * 225);
-                else B.co_H12.resize(B.co_H12.size() + 225, 0.0);
-            }
-            for (int q = 0; q < 3; q++) B.co_pbgw.push_back(w->pbg[q]);
-            for (int q = 0; q < 3; q++) B.co_pbgw.push_back(w->gw[q]);
-            io += 4 + N; pn += 15LL * M * N; nn += (long long)N * N; no += N; e0 += M;
-        }
-        hw.comp_ne = e0;
-    }
-#undef CHK
-    R.gf1 = (int)B.gf.size();
-
-    // ---- cliques
-    R.cl0 = (int)B.cl.size();
-    std::map<int, int> e_clique;            // window block id -> clique
-    std::map<int, int> free_clique;         // first variable block -> clique (free factors)
-    struct TmpC { int e; std::vector<int> facs; std::vector<int> mem; bool is_static; };
-    std::vector<TmpC> tc;
-    // group-0 non-landmark blocks, in ordering order, always get a clique
-    for (int i = 0; i < w->n_order; i++) {
-        int b = w->order_block[i];
-        if (w->order_group[i] != 0) break;
-        if (b >= nP + nS && b < nP + nS + nL && !lm_generic[b - nP - nS]) continue;      // fast-path landmarks: k_lm_schur
-        e_clique[b] = (int)tc.size();
-        tc.push_back(TmpC{ b, {}, {}, false });
-    }
-    for (int f = R.gf0; f < R.gf1; f++) {
-        const TmpF& t = tf[f - R.gf0];
-        int e = -1, first_var = -1;
-        for (int b : t.blk) {
-            if (loc[b] < 0) continue;
-            if (first_var < 0) first_var = b;
-            if (is_e(b)) {
-                if (b >= nP + nS && b < nP + nS + nL && !lm_generic[b - nP - nS]) return fail(SWF_E_UNSUPPORTED, "non-projection factor on a landmark");
-                if (e >= 0 && e != b) return fail(SWF_E_INVALID, "elimination group 0 is not an independent set");
-                e = b;
-            }
-        }
-        int c;
-        if (e >= 0) c = e_clique[e];
-        else if (B.gf[f].type == GF_PRIOR) { c = (int)tc.size(); tc.push_back(TmpC{ -1, {}, {}, true }); }
-        else if (first_var < 0) continue;    // all-constant factor: contributes only to the cost
-        else {
-            auto it = free_clique.find(first_var);
-            if (it == free_clique.end()) { c = (int)tc.size(); free_clique[first_var] = c; tc.push_back(TmpC{ -1, {}, {}, false }); }
-            else c = it->second;
-        }
-        tc[c].facs.push_back(f);
-        for (int b : t.blk) {
-            if (loc[b] < 0 || b == e) continue;
-            if (std::find(tc[c].mem.begin(), tc[c].mem.end(), b) == tc[c].mem.end()) tc[c].mem.push_back(b);
-        }
-    }
-    // reduced offsets
-    auto red = [&](int b) { return loc[b] - ne; };
-    std::map<std::pair<int, int>, std::vector<std::array<long long, 3>>> pmap;   // (a,b) -> (coff, cld, voff)
-    for (size_t ci = 0; ci < tc.size(); ci++) {
-        TmpC& t = tc[ci];
-        Clique C{};
-        C.win = wi;
-        C.d_e = t.e >= 0 ? ls[t.e] : 0;
-        C.e_loc = t.e >= 0 ? gloc(t.e) : -1;
-        C.fac0 = (int)B.cl_fac.size();
-        int nrows = 0;
-        for (int f : t.facs) { B.cl_fac.push_back(f); B.cl_frow.push_back(nrows); nrows += B.gf[f].nres; B.gf[f].clique = (int)B.cl.size(); }
-        C.fac1 = (int)B.cl_fac.size();
-        C.n_rows = nrows;
-
-        C.mem0 = (int)B.cm_loc.size();
-        int df = 0;
-        std::map<int, int> colof;
-        for (int b : t.mem) {
-            B.cm_loc.push_back(gloc(b)); B.cm_ls.push_back(ls[b]); B.cm_col.push_back(df);
-            colof[b] = df; df += ls[b];
-        }
-        C.mem1 = (int)B.cm_loc.size();
-        C.d_f = df;
-        if (!t.is_static && C.d_e + df > CB_MAXD) return fail(SWF_E_UNSUPPORTED, "clique with more than 768 columns");
-        if (!t.is_static && C.d_e > 9) return fail(SWF_E_UNSUPPORTED, "group-0 block larger than 9 dimensions");
-        // (k_clique_big keeps the e-rows of M and T = Einv M_ef in LDS: only the cliques that take it — beyond 64 x 64 / 96 x 64 — are bound by that)
-        if (!t.is_static && (nrows > CLQ_TALLR || C.d_e + df > 64) && (long long)C.d_e * (C.d_e + df) > CB_MAXED)
-            return fail(SWF_E_UNSUPPORTED, "clique beyond one wavefront with d_e (d_e + d_f) > 1536 (swf_solver.h: limits of a group-0 clique)");
-        C.C_off = B.C_tot; B.C_tot += (long long)df * df;
-        C.v_off = B.v_tot; B.v_tot += df;
-        C.e_off = B.e_tot; B.e_tot += C.d_e * C.d_e + C.d_e * df + C.d_e;
-        C.is_static = t.is_static ? 1 : 0;
-        // slot -> clique column
-        for (int f : t.facs) {
-            const TmpF& tff = tf[f - R.gf0];
-            for (size_t sl = 0; sl < tff.blk.size(); sl++) {
-                int b = tff.blk[sl];
-                int cc = -1;
-                if (loc[b] >= 0) cc = (b == t.e) ? 0 : C.d_e + colof[b];
-                B.s_ccol[B.gf[f].slot0 + sl] = cc;
-            }
-        }
-        // storage: a non-static clique owns a dense column-major Jacobian [d][n_rows] in g_J (each factor's blocks sit at
-        // their (row, column) position, column stride n_rows) and contiguous residual rows in g_r; factors of static cliques
-        // only need residual rows
-        C.r_off = B.r_tot; B.r_tot += nrows;
-        C.j_off = B.j_tot;
-        {
-            int dcl = C.d_e + df, frow = 0;
-            for (int f : t.facs) {
-                GFac& G = B.gf[f];
-                G.roff = C.r_off + frow; G.jld = nrows;
-                for (int sl = 0; sl < G.nslot; sl++) {
-                    int cc = B.s_ccol[G.slot0 + sl];
-                    // a prior-type record inside the clique of a group-0 block (a composite factor on an eliminated speed-bias block, as
-                    // MyOrdering produces them, R/swf/swf_gnss.cpp:683-691): its rows join the clique's dense Jacobian like any factor's —
-                    // the prior evaluation copies the record's columns there at every linearisation
-                    if (G.type == GF_PRIOR && !t.is_static && cc >= 0) B.s_joff[G.slot0 + sl] = 0;
-                    if (B.s_joff[G.slot0 + sl] < 0) continue;
-                    if (t.is_static || cc < 0) { B.s_joff[G.slot0 + sl] = -1; continue; }
-                    B.s_joff[G.slot0 + sl] = C.j_off + cc * nrows + frow;
-                }
-                frow += G.nres;
-            }
-            if (!t.is_static) B.j_tot += nrows * dcl;
-        }
-        // static prior clique: C = J^T J over member columns, dgraw = diag
-        B.C_init.resize((size_t)B.C_tot, 0.0);
-        B.dgraw_init.resize((size_t)B.v_tot, 0.0);
-        if (t.is_static) {
-            const GFac& G = B.gf[t.facs[0]];
-            int dim = G.nres;
-            const double* J = B.prior_J.data() + B.prior_Joff[G.data];
-            // prior column -> member column (or -1)
-            std::vector<int> pcol(dim, -1);
-            {
-                int col = 0;
-                const TmpF& tff = tf[t.facs[0] - R.gf0];
-                for (int b : tff.blk) { if (loc[b] >= 0) for (int j = 0; j < ls[b]; j++) pcol[col + j] = colof[b] + j; col += ls[b]; }
-            }
-            double* Cm = B.C_init.data() + C.C_off;
-            for (int a = 0; a < dim; a++) {
-                if (pcol[a] < 0) continue;
-                for (int b2 = 0; b2 < dim; b2++) {
-                    if (pcol[b2] < 0) continue;
-                    double sacc = 0;
-                    for (int r = 0; r < dim; r++) sacc += J[(size_t)r * dim + a] * J[(size_t)r * dim + b2];
-                    Cm[(size_t)pcol[a] * df + pcol[b2]] = sacc;
-                }
-                B.dgraw_init[C.v_off + pcol[a]] = Cm[(size_t)pcol[a] * df + pcol[a]];
-            }
-        }
-        // pair contributions
-        for (int a : t.mem) for (int b2 : t.mem) {
-            if (red(a) < red(b2)) continue;
-            pmap[{ a, b2 }].push_back({ C.C_off + (long long)colof[a] * df + colof[b2], df, C.v_off + colof[a] });
-        }
-        B.cl.push_back(C);
-    }
-    R.cl1 = (int)B.cl.size();
-    // factors outside every clique (all blocks constant) still own residual rows (cost only)
-    for (int f = R.gf0; f < R.gf1; f++) if (B.gf[f].roff < 0) { B.gf[f].roff = B.r_tot; B.r_tot += B.gf[f].nres; }
-
-    // ---- pairs: clique pairs, all frame pairs, a diagonal pair for every reduced block
-    for (int p = 0; p < nP; p++) if (frame_of[p] >= 0)
-        for (int q = 0; q < nP; q++) if (frame_of[q] >= 0 && red(bidP(p)) >= red(bidP(q))) pmap[{ bidP(p), bidP(q) }];
-    for (int i = 0; i < w->n_order; i++) { int b = w->order_block[i]; if (!is_e(b)) pmap[{ b, b }]; }
-    R.pair0 = (int)B.pair.size();
-    for (auto& kv : pmap) {
-        int a = kv.first.first, b2 = kv.first.second;
-        Pair P{};
-        P.win = wi; P.ra = red(a); P.rb = red(b2); P.la = ls[a]; P.lb = ls[b2];
-        P.fa = a < nP ? frame_of[a] : -1; P.fb = b2 < nP ? frame_of[b2] : -1;
-        P.c0 = (int)B.pc_coff.size();
-        for (auto& c : kv.second) { B.pc_coff.push_back(c[0]); B.pc_cld.push_back((int)c[1]); B.pc_voff.push_back((int)c[2]); }
-        P.c1 = (int)B.pc_coff.size();
-        P.is_diag = (a == b2) ? 1 : 0;
-        P.loc_a = gloc(a);
-        B.pair.push_back(P);
-    }
-    R.pair1 = (int)B.pair.size();
-
-    R.proj_sqrt_info = w->proj_sqrt_info; R.proj_loss_a = w->proj_loss_a;
-    for (int k = 0; k < 3; k++) { R.pbg[k] = w->pbg[k]; R.gw[k] = w->gw[k]; R.base[k] = w->base[k]; }
-    B.n_x += R.x_n; B.n_loc += R.n_loc;
-    // algorithmic Jacobian bytes of one evaluation (SURVEY.md §8d formula)
-    {
-        int64_t pb = 0;
-        for (int k = 0; k < w->n_prior; k++) { int64_t n = w->prior_dim[k]; pb += 8 * (n * n + 4 * n); }
-        B.jac_bytes += (int64_t)312 * w->n_proj + (int64_t)5480 * w->n_imu + (int64_t)176 * w->n_cp + (int64_t)152 * w->n_pr + (int64_t)208 * w->n_dop
-                     + (int64_t)136 * w->n_spr + (int64_t)160 * w->n_scp + (int64_t)56 * w->n_fix + (int64_t)584 * w->n_idp + pb;
-    }
-    B.win.push_back(R);
-    return SWF_OK;
-}
-}  // namespace
-
 // ------------------------------------------------------------------ batch API
+// The symbolic phase is swf_plan.cpp (host-only): this function uploads a Plan and computes none of its tables.  The data slabs take
+// the tables in a fixed order (put), the zero slabs the mutable buffers (zeros); one copy per data slab and one memset per zero slab.
 extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n, void* stream, swf_batch** out) {
     if (!windows || n <= 0 || !out) return fail(SWF_E_INVALID, "swf_batch_create: bad arguments");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(SWF_E_NODEVICE, "no HIP device: this library has no CPU fallback");
-    Build B;
-    std::vector<HostWin> hw(n);
-    for (int i = 0; i < n; i++) {
-        int rc = build_window(B, windows[i], i, hw[i]);
-        if (rc != SWF_OK) return rc;
-    }
-    if (B.n_x > 0x7fffffffLL || B.n_loc > 0x7fffffffLL) return fail(SWF_E_UNSUPPORTED, "batch too large for 32-bit offsets");
-    swf_batch* b = new swf_batch();
-    b->device = current_device();
-    b->stream = (hipStream_t)stream;
-    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) b->n_cu = pr.multiProcessorCount; }
-    b->D.rr_nmax = b->rr_nmax;
+    int n_cu = 256;
+    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) n_cu = pr.multiProcessorCount; }
     // (the launch-shape knobs that remain are test aids, each exercised by the GPU tier, and are read once, here: no getenv on the latency
     // path or inside the marginalisation's sweep loop, and none that could race a setenv from the per-device enqueue threads of
     // swf_solve_batches.  Nothing that changes RESULTS is an environment variable: those are fields of swf_options.)
+    Plan B;
+    {
+        std::string err;
+        int prc = plan_build(windows, n, plan_shape_from_env(n_cu), B, err);
+        if (prc != SWF_OK) return fail(prc, err);
+    }
+    std::unique_ptr<swf_batch> owner(new swf_batch());
+    swf_batch* b = owner.get();
+    b->device = current_device();
+    b->stream = (hipStream_t)stream;
+    b->n_cu = n_cu;
     b->no_comp_fuse = getenv("SWF_NO_COMP_FUSE") != nullptr;
     b->no_spec = getenv("SWF_NO_SPEC_EVAL") != nullptr;
     b->no_step_fuse = getenv("SWF_NO_STEP_FUSE") != nullptr;
     b->no_decide_fuse = getenv("SWF_NO_DECIDE_FUSE") != nullptr;
     b->full_final = getenv("SWF_FULL_FINAL_ELIM") != nullptr;
-    // auxiliary stream: the latency path (<= n_CU / 16 windows), and batches of half a chip to a chip of windows, where the IMU / clique branch
-    // fills what one-block-per-window kernels leave idle (measured: 256 windows 5.52 -> 5.22 ms, 128 windows 3.73 -> 3.49 ms per solve; 64 and
-    // 512 windows: no gain)
-    // latency path (up to n_CU / 8 windows): independent kernels of an iteration ride in ONE grid (the IMU factors with the projection /
-    // scalar factors, every clique size class in one launch) on ONE stream.  Round 3 ran the IMU / clique branch of such batches on the
-    // auxiliary stream instead; the kernel trace shows what that buys: every cross-queue edge (event record -> stream wait) costs 6-13 us
-    // of dependency resolution, as much as the overlap saves (one window: 1.432 ms with the auxiliary stream, 1.443 without).
-    b->lat_fuse = n * 8 <= b->n_cu && !getenv("SWF_NO_LAT_FUSE");
-    if ((n * 16 <= b->n_cu && !b->lat_fuse) || (2 * n >= b->n_cu && n <= b->n_cu)) {            // fork / join inside a linearisation
+    // what the launcher reads of the plan
+    b->max_tiles = B.max_tiles; b->max_prior_dim = B.max_prior_dim; b->max_red = B.max_red; b->min_red = B.min_red;
+    b->rr_nmax = B.rr_nmax; b->rr4_has15 = B.rr4_has15; b->rr4_has16 = B.rr4_has16; b->n_pch_split = B.n_pch_split;
+    b->lat_fuse = B.lat_fuse; b->asm_programs = B.asm_programs;
+    b->ls_qpb = B.ls_qpb; b->ls_var = B.ls_var; b->ls_kms = B.ls_kms; b->ls_gqpb = B.ls_gqpb; b->ls_folded = B.ls_folded; b->s_direct = B.s_direct;
+    for (int k = 0; k < 5; k++) b->clc_imu[k] = B.clc_imu[k];
+    b->n_comp = B.n_comp; b->comp_nmax = B.comp_nmax; b->comp_nmin = B.comp_nmin; b->comp_ne = B.comp_ne;
+    b->jac_bytes = B.jac_bytes; b->proj_bytes = B.proj_bytes; b->chol_flops = B.chol_flops;
+    b->lm_schur_flops = B.lm_schur_flops; b->lm_schur_flops_sym = B.lm_schur_flops_sym; b->lm_schur_mfma = B.lm_schur_mfma;
+    if (B.want_aux) {                                      // fork / join inside a linearisation
         bool ok = (b->aux = handle_cache().stream()) != nullptr;
         for (int i = 0; i < 3 && ok; i++) ok = (b->ev_fork[i] = handle_cache().event(false)) != nullptr;
         if (!ok) { handle_cache().give(b->aux); b->aux = nullptr; }
     }
-    b->win = B.win; b->hw = hw; b->max_tiles = B.max_tiles; b->max_prior_dim = B.max_prior_dim; b->jac_bytes = B.jac_bytes;
-    b->proj_bytes = (int64_t)312 * (int64_t)B.p_win.size();
-    for (size_t l = 0; l + 1 < B.lm_obs0.size() + 1 && l < B.lm_win.size(); l++) {
-        int64_t k = (l + 1 < B.lm_obs0.size() ? B.lm_obs0[l + 1] : (int)B.p_win.size()) - B.lm_obs0[l];
-        b->lm_schur_flops += 216 * k * k + 108 * k;
-        b->lm_schur_flops_sym += 108 * k * (k - 1) + 162 * k;
-    }
-    for (auto& W : B.win) { b->chol_flops += (int64_t)W.n_red * W.n_red * W.n_red / 3; b->max_red = std::max(b->max_red, W.n_red); b->min_red = std::min(b->min_red, W.n_red); if (W.n_red > 224 && W.n_red <= 240) b->rr4_has15 = true; if (W.n_red > 240 && W.n_red <= 256) b->rr4_has16 = true; }
     DevBatch& D = b->D;
     DevPool& P = b->pool;
     int rc = 0;
-    D.n_win = n; D.n_x = (int)B.n_x; D.n_loc_total = (int)B.n_loc; D.max_iter_trace = SWF_MAX_TRACE;
-    std::vector<int> lmb_lr;
+    D.n_win = n; D.n_x = (int)B.n_x; D.n_loc_total = (int)B.n_loc; D.max_iter_trace = SWF_MAX_TRACE; D.rr_nmax = B.rr_nmax;
+    D.n_lmb = B.n_lmb; D.n_pch = B.n_pch; D.n_proj = B.n_proj; D.n_lm = B.n_lm; D.n_fr = B.n_fr; D.n_fsb = B.n_fsb;
+    D.n_gf = (int)B.gf.size(); D.n_imu = (int)B.imu_gf.size(); D.n_sc = (int)B.sc_gf.size(); D.n_prior = (int)B.prior_gf.size(); D.n_idp = (int)B.idp_gf.size();
+    D.n_cl = (int)B.cl.size(); D.n_pair = (int)B.pair.size(); D.n_pd = B.n_pd; D.n_po = B.n_po; D.n_cle = B.n_cle;
+    for (int k = 0; k < 5; k++) D.n_clc[k] = B.n_clc[k];
+    D.as_max_ne = B.as_max_ne; D.as_max_nv = B.as_max_nv;
+    // ---- the tables: ONE upload section, in the order the data slabs have always had
+#define PUT(field) rc |= P.put(B.field, &D.field)
+    PUT(win);
+    PUT(lmb_rec); PUT(pch_q); PUT(pch_r0); PUT(prior_nch);
+    PUT(blk_xoff); PUT(blk_loc); PUT(blk_gs);
+    PUT(loc2x); PUT(x_var);
+    PUT(p_win); PUT(p_xpose); PUT(p_xex); PUT(p_xlm);
+    PUT(p_lpose); PUT(p_llm); PUT(p_fr); PUT(p_lm); PUT(p_uv);
+    PUT(lm_win); PUT(lm_obs0); PUT(lm_loc); PUT(lm_col); PUT(lm_fmask);
+    PUT(sch_c0); PUT(sch_rec); PUT(sch_km);
+    PUT(fr_obs0); PUT(fr_obs); PUT(fr_red);
+    PUT(fsb_rec);
+    PUT(fsb_perm); PUT(fsb_foff);
+    PUT(gf);
+    PUT(s_x); PUT(s_loc); PUT(s_ls); PUT(s_joff); PUT(s_ccol);
+    PUT(imu_pre); PUT(cp_dat); PUT(pr_dat); PUT(dop_dat); PUT(sp_w); PUT(gx_dat);
+    PUT(imu_gf); PUT(sc_gf); PUT(prior_gf); PUT(idp_gf);
+    PUT(sc_jt); PUT(imu_jt);
+    PUT(prior_dim); PUT(prior_Joff); PUT(prior_roff); PUT(prior_x0off);
+    PUT(prior_Jt);
+    PUT(prior_colloc); PUT(prior_colcc); PUT(s_pcol); PUT(s_pxo);
+    PUT(prior_J); PUT(prior_r0); PUT(prior_x0);
+    PUT(cl); PUT(cl_fac); PUT(cl_frow); PUT(cm_loc); PUT(cm_ls); PUT(cm_col);
+    PUT(cv_loc);
+    PUT(pc_coff); PUT(pc_cld); PUT(pc_voff);
+    PUT(asw); PUT(s_tnz);
+    PUT(as_dst); PUT(as_cnt); PUT(as_src0); PUT(as_aux); PUT(as_src);
+    PUT(av_loc); PUT(av_red); PUT(av_cnt); PUT(av_src0); PUT(av_i); PUT(av_src);
+    PUT(pair_d); PUT(pair_o);
+    PUT(cle_rec);
+    for (int k = 0; k < 5; k++) PUT(clc_rec[k]);
+#undef PUT
     {
-        // landmark back-substitution blocks: consecutive landmarks of one window with at most 256 observations together
-        // (built before the window records are uploaded: a window knows its block range, WinRec::lmb0 / lmb1)
-        std::vector<int>& lr = lmb_lr;
-        std::vector<int> obs0 = B.lm_obs0; obs0.push_back((int)B.p_win.size());
-        for (WinRec& Wr : B.win) {
-            Wr.lmb0 = (int)(lr.size() / 4);
-            int l = Wr.lm0;
-            while (l < Wr.lm1) {
-                const int o0 = obs0[(size_t)l]; int l1 = l, cnt = 0;
-                while (l1 < Wr.lm1 && l1 - l < 256 && cnt + (obs0[(size_t)l1 + 1] - obs0[(size_t)l1]) <= 256) { cnt += obs0[(size_t)l1 + 1] - obs0[(size_t)l1]; l1++; }
-                if (l1 == l) { P.release(); delete b; return fail(SWF_E_UNSUPPORTED, "landmark with more than 256 observations"); }
-                lr.push_back(o0); lr.push_back(cnt); lr.push_back(l); lr.push_back(l1 - l);
-                l = l1;
-            }
-            Wr.lmb1 = (int)(lr.size() / 4);
-        }
-        D.n_lmb = (int)(lr.size() / 4);
-        if (lr.empty()) lr.resize(4, 0);
+        const double* ci = nullptr; const double* di = nullptr;
+        rc |= P.put(B.C_init, &ci); rc |= P.put(B.dgraw_init, &di);
+        D.C = (double*)ci; D.cv_dgraw = (double*)di;
     }
-    std::vector<int> pch_q, pch_r0, prior_nch;
-    {
-        // row chunks of the priors (swf_dev.h): a prior beyond PRIOR_SPLIT_DIM rows is evaluated by one workgroup per PRIOR_CHUNK rows;
-        // a window's priors (the composite factors' records among them) are contiguous in prior_gf, and so are their chunks
-        for (WinRec& Wr : B.win) { Wr.pch0 = 0; Wr.pch1 = 0; }
-        int cur_w = -1;
-        for (size_t q = 0; q < B.prior_gf.size(); q++) {
-            const GFac& G = B.gf[(size_t)B.prior_gf[q]];
-            const int n = G.nres, nch = n > PRIOR_SPLIT_DIM ? (n + PRIOR_CHUNK - 1) / PRIOR_CHUNK : 1;
-            if (G.win != cur_w) { cur_w = G.win; B.win[(size_t)cur_w].pch0 = (int)pch_q.size(); }
-            prior_nch.push_back(nch);
-            for (int c = 0; c < nch; c++) { pch_q.push_back((int)q); pch_r0.push_back(nch > 1 ? c * PRIOR_CHUNK : 0); }
-            B.win[(size_t)cur_w].pch1 = (int)pch_q.size();
-            if (nch > 1 && G.clique >= 0 && B.cl[(size_t)G.clique].is_static) b->n_pch_split += nch;
-        }
-        D.n_pch = (int)pch_q.size();
-        if (pch_q.empty()) { pch_q.push_back(0); pch_r0.push_back(0); }
-        if (prior_nch.empty()) prior_nch.push_back(1);
-        b->win = B.win;                                   // (the host's copy of the records, with the block ranges)
+    // composite IMU-GNSS factors: operator arguments over the whole batch + where each factor's prior record and clique live
+    CompArgs& A = b->CA; CompMeta& Mt = b->CM;
+    const int nc = B.n_comp;
+    if (nc) {
+        A.n = nc; A.want_jac = 1; A.n_iq = (int)B.co_iq_f.size();
+        rc |= P.put(B.co_M, &A.M); rc |= P.put(B.co_N, &A.N); rc |= P.put(B.co_eo, &A.e_off); rc |= P.put(B.co_no, &A.n_off);
+        rc |= P.put(B.co_pno, &A.pn_off); rc |= P.put(B.co_nno, &A.nn_off); rc |= P.put(B.co_go, &A.g_off); rc |= P.put(B.co_g2o, &A.g2_off);
+        { const double* t1 = nullptr; const double* t2 = nullptr; rc |= P.put(B.co_pose, &t1); rc |= P.put(B.co_sb, &t2); A.pose = (double*)t1; A.sb = (double*)t2; }
+        { const double* t1 = nullptr; const double* t2 = nullptr; rc |= P.put(B.co_pose, &t1); rc |= P.put(B.co_sb, &t2); b->co_pose0 = (double*)t1; b->co_sb0 = (double*)t2; }
+        rc |= P.put(B.co_pose_lin, &A.pose_lin); rc |= P.put(B.co_sb_lin, &A.sb_lin); rc |= P.put(B.co_Hpp, &A.Hpp); rc |= P.put(B.co_HpN, &A.HpN);
+        rc |= P.put(B.co_rhs_p, &A.rhs_p); rc |= P.put(B.co_HNN, &A.HNN); rc |= P.put(B.co_rhsN, &A.rhsN); rc |= P.put(B.co_pre, &A.pre); rc |= P.put(B.co_pbgw, &A.pbgw);
+        rc |= P.put(B.co_mid, &A.mid); rc |= P.put(B.co_H12, &A.H12);
+        rc |= P.put(B.co_iq_f, &A.iq_f); rc |= P.put(B.co_iq_k, &A.iq_k);
+        rc |= P.put(B.co_win, &Mt.win); rc |= P.put(B.co_xo_off, &Mt.xo_off); rc |= P.put(B.co_xo, &Mt.xo);
+        rc |= P.put(B.co_Joff, &Mt.Joff); rc |= P.put(B.co_roff, &Mt.roff); rc |= P.put(B.co_x0off, &Mt.x0off); rc |= P.put(B.co_Coff, &Mt.Coff); rc |= P.put(B.co_voff, &Mt.voff);
+        Mt.prior_J = (double*)D.prior_J; Mt.prior_Jt = (double*)D.prior_Jt; Mt.prior_r0 = (double*)D.prior_r0; Mt.prior_x0 = (double*)D.prior_x0;
     }
-#define PUT(field, vec) rc |= P.put(vec, &D.field)
-    PUT(win, B.win);
-    PUT(lmb_rec, lmb_lr); PUT(pch_q, pch_q); PUT(pch_r0, pch_r0); PUT(prior_nch, prior_nch);
-    PUT(blk_xoff, B.blk_xoff); PUT(blk_loc, B.blk_loc); PUT(blk_gs, B.blk_gs);
-    if (B.loc2x.empty()) B.loc2x.push_back(-1);
-    PUT(loc2x, B.loc2x); PUT(x_var, B.x_var);
-    D.n_proj = (int)B.p_win.size();
-    PUT(p_win, B.p_win); PUT(p_xpose, B.p_xpose); PUT(p_xex, B.p_xex); PUT(p_xlm, B.p_xlm);
-    PUT(p_lpose, B.p_lpose); PUT(p_llm, B.p_llm); PUT(p_fr, B.p_fr); PUT(p_lm, B.p_lm); PUT(p_uv, B.p_uv);
-    D.n_lm = (int)B.lm_win.size();
-    B.lm_obs0.push_back(D.n_proj);
-    PUT(lm_win, B.lm_win); PUT(lm_obs0, B.lm_obs0); PUT(lm_loc, B.lm_loc); PUT(lm_col, B.lm_col); PUT(lm_fmask, B.lm_fmask);
-    {
-        // k_lm_schur's launch shape: the row class of the panel by the batch's largest window (<= 10 / 21 / 42 / 64 observing frames) and
-        // the landmark parts per block — as many as still leave >= 2 blocks per CU.  SWF_LS_VARIANT / SWF_LS_QPB: test / debugging aids.
-        // A block that covers all parts folds them in registers (ls_folded) and, in that case, writes -P straight into S (s_direct); the
-        // off-diagonal frame pairs without any other contribution then leave the assembly's list.
-        const int force = getenv("SWF_LS_VARIANT") ? atoi(getenv("SWF_LS_VARIANT")) : 0;
-        const int force_qpb = getenv("SWF_LS_QPB") ? atoi(getenv("SWF_LS_QPB")) : 0;
-        int qpb = 1;
-        while (qpb < GEMM_SPLIT && (long long)n * GEMM_SPLIT / (2 * qpb) >= 2LL * b->n_cu) qpb *= 2;
-        // from half a chip of windows on, one block per window: the folded product and the direct-to-S write-out are worth more than the
-        // second round of blocks
-        if (2LL * n >= b->n_cu) qpb = GEMM_SPLIT;
-        if (force_qpb >= 1 && force_qpb <= GEMM_SPLIT && (force_qpb & (force_qpb - 1)) == 0) qpb = force_qpb;
-        b->ls_qpb = qpb;
-        b->ls_var = (b->max_tiles <= 10 && force < 1) ? 0 : (b->max_tiles <= 36 && force < 2) ? 1 : (b->max_tiles <= 136 && force < 3) ? 2 : 3;
-        b->ls_folded = qpb == GEMM_SPLIT && b->ls_var <= 1;          // must mirror CAN_FOLD in k_lm_schur
-        b->s_direct = b->ls_folded;
-        // the gradient-only pass of the final linearisation: never more parts per workgroup than the product kernel takes (the latency path
-        // keeps its spread of a window over the chip).  SWF_LS_GRAD_QPB: test / measuring aid.
-        const int force_gqpb = getenv("SWF_LS_GRAD_QPB") ? atoi(getenv("SWF_LS_GRAD_QPB")) : 0;
-        b->ls_gqpb = std::min(qpb, LS_GRAD_QPB);
-        if (force_gqpb >= 1 && force_gqpb <= GEMM_SPLIT && (force_gqpb & (force_gqpb - 1)) == 0) b->ls_gqpb = force_gqpb;
-    }
-    {
-        // k_lm_schur task table.  A wave task = the four 16-lane groups of one producer wave = four landmarks, one group and three of the
-        // task's twelve panel columns each (a track of more than 16 observations takes further rounds of its group's lanes).  Record of
-        // (task, group): L (-1 = empty), loc, first / end observation of the landmark, first column within the task (0, 3, 6, 9).  The window's landmarks
-        // enter in the order of their tile footprint (last, first 16-row tile of the reduced camera matrix they touch), so the landmarks of a
-        // task mostly share theirs; bit g of the tile mask of (chunk, tile) — some landmark of the chunk's wave task g is seen from the tile's
-        // row frames and from its column frames, per k-step of the task since round 4 (three bits per task: a tile skips the k-steps none of
-        // whose landmarks touch it) — is what the consumer waves walk (a chunk = TW tasks, by size class; the packing into tasks
-        // and the parts, which end on even task numbers, are the same in every class: so is every sum).  Tile list of a window: the nt
-        // diagonal tiles, then (tr > tc) row by row.
-        const int TW = b->ls_var <= 1 ? 2 : 1;
-        const int NCW = b->ls_var <= 1 ? 8 : 12, TPW = b->ls_var == 0 ? 2 : b->ls_var == 1 ? 5 : 6;
-        const int n_launch = std::max(1, (b->max_tiles + NCW * TPW - 1) / (NCW * TPW));
-        b->ls_kms = n_launch * NCW;                                  // mask words per chunk
-        std::vector<int> c0, rec, km;
-        std::vector<std::vector<unsigned>> task_tiles;               // per task of the current window: tile-list entries it touches
-        for (auto& W : B.win) {
-            const int m = 6 * W.nF, nt = (m + 15) / 16, ntl = nt * (nt + 1) / 2;
-            auto tile_rows = [&](unsigned long long fm) {          // 16-row tiles the frames of fm touch
-                unsigned t = 0;
-                for (int f = 0; f < W.nF && f < 64; f++) if ((fm >> f) & 1ULL) { t |= 1u << ((6 * f) / 16); t |= 1u << ((6 * f + 5) / 16); }
-                return t;
-            };
-            std::vector<int> ord; std::vector<unsigned> trs((size_t)(W.lm1 - W.lm0), 0u);
-            for (int l = W.lm0; l < W.lm1; l++) {
-                if (B.lm_loc[l] < 0) continue;                     // constant landmark: nothing to eliminate
-                int k = B.lm_obs0[l + 1] - B.lm_obs0[l];
-                if (k > 64) { P.release(); delete b; return fail(SWF_E_UNSUPPORTED, "landmark with more than 64 observations"); }
-                trs[(size_t)(l - W.lm0)] = tile_rows(B.lm_fmask[l]);
-                ord.push_back(l);
-            }
-            auto key = [&](int l) { unsigned t = trs[(size_t)(l - W.lm0)]; int lo = t ? __builtin_ctz(t) : 0, hi = t ? 31 - __builtin_clz(t) : 0; return hi * 64 + lo; };
-            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return key(x) < key(y); });
-            const int first_task = (int)(rec.size() / 32);
-            task_tiles.clear();
-            size_t at = 0; int lw = 4;                             // force a new task at the first landmark
-            auto new_task = [&]() { at = rec.size(); rec.resize(at + 32, 0); for (int g = 0; g < 4; g++) rec[at + g * 8] = -1; task_tiles.emplace_back((size_t)ntl, 0u); lw = 0; };
-            for (int l : ord) {
-                int o0 = B.lm_obs0[l], k = B.lm_obs0[l + 1] - o0;
-                if (lw >= 4) new_task();
-                int* r = &rec[at + (size_t)lw * 8];                 // group lw of the task = this landmark, whatever its track length
-                r[0] = l; r[1] = B.lm_loc[l]; r[2] = o0; r[3] = o0 + k; r[4] = 3 * lw; r[5] = 0; r[6] = 0; r[7] = 0;
-                // tile-list entries this landmark touches, as the k-steps of the task that carry its three columns (columns 3 lw .. 3 lw + 2 of
-                // the task's twelve; a k-step = four columns): group 0 -> k-step 0, group 1 -> 0 and 1, group 2 -> 1 and 2, group 3 -> 2
-                unsigned t = trs[(size_t)(l - W.lm0)];
-                const unsigned ks = lw == 0 ? 1u : lw == 1 ? 3u : lw == 2 ? 6u : 4u;
-                std::vector<unsigned>& tt = task_tiles.back();
-                for (int tr = 0; tr < nt; tr++) {
-                    if (!((t >> tr) & 1u)) continue;
-                    tt[(size_t)tr] |= ks;
-                    for (int tc = 0; tc < tr; tc++) if ((t >> tc) & 1u) tt[(size_t)(nt + tr * (tr - 1) / 2 + tc)] |= ks;
-                }
-                lw++;
-            }
-            if (task_tiles.size() & 1) new_task();                 // an even number of tasks per window
-            const int ntask = (int)task_tiles.size();
-            // masks: chunk c of this window = tasks [c TW, (c + 1) TW)
-            for (int c = 0; c < ntask / TW; c++) {
-                size_t kw = km.size(); km.resize(kw + (size_t)b->ls_kms, 0);
-                for (int g = 0; g < TW; g++) {
-                    const std::vector<unsigned>& tt = task_tiles[(size_t)(c * TW + g)];
-                    for (int e = 0; e < ntl; e++) if (tt[(size_t)e]) {
-                        b->lm_schur_mfma += __builtin_popcount(tt[(size_t)e]);
-                        int lp = e / (NCW * TPW), r = e % (NCW * TPW), sl = r / NCW, cw = r % NCW;
-                        km[kw + (size_t)(lp * NCW + cw)] |= (tt[(size_t)e] << (3 * g)) << (3 * TW * sl);
-                    }
-                }
-            }
-            // part sp = task pairs [sp np / 16, (sp + 1) np / 16): the parts differ by at most one pair, so any grouping of consecutive parts
-            // into workgroups (qpb = 1 .. 16, by batch size) is balanced
-            const int np = ntask / 2;
-            for (int sp = 0; sp < GEMM_SPLIT; sp++) c0.push_back(first_task + 2 * (int)((long long)sp * np / GEMM_SPLIT));
-        }
-        c0.push_back((int)(rec.size() / 32));
-        rec.resize(rec.size() + (size_t)32 * 4 * LS_NB, 0);           // slack behind the table
-        km.resize(km.size() + (size_t)b->ls_kms * 2, 0);
-        PUT(sch_c0, c0); PUT(sch_rec, rec); PUT(sch_km, km);
-    }
-    D.n_fr = B.n_fr;
-    B.fr_obs0.push_back((int)B.fr_obs.size());
-    PUT(fr_obs0, B.fr_obs0); PUT(fr_obs, B.fr_obs); PUT(fr_red, B.fr_red);
-    D.n_fsb = (int)B.fsb_win.size();
-    B.fsb_obs0.push_back(D.n_proj); B.fsb_perm.resize((size_t)D.n_proj + 1, 0);
-    {
-        // one 32-byte record per frame-sum block (layout: ProjBlk, swf_kernels.h): everything the block's evaluation needs to address its loads comes with ONE load
-        std::vector<int> rec((size_t)8 * std::max(D.n_fsb, 1), 0);
-        for (int k = 0; k < D.n_fsb; k++) {
-            int* r = rec.data() + (size_t)8 * k;
-            r[0] = B.fsb_win[(size_t)k]; r[1] = B.fsb_obs0[(size_t)k]; r[2] = B.fsb_obs0[(size_t)k + 1] - B.fsb_obs0[(size_t)k];
-            r[3] = B.fsb_foff0[(size_t)k]; r[4] = B.fsb_out0[(size_t)k]; r[5] = B.win[(size_t)r[0]].nF;
-        }
-        PUT(fsb_rec, rec);
-    }
-    PUT(fsb_perm, B.fsb_perm); PUT(fsb_foff, B.fsb_foff);
+    // ---- the mutable buffers: zero slabs
     rc |= P.zeros((size_t)B.fs_tot * FS_VAL, &D.fs_part);
     rc |= P.zeros((size_t)std::max<long long>(B.n_loc, 1), &D.jsc);
-    D.n_gf = (int)B.gf.size();
-    PUT(gf, B.gf);
-    PUT(s_x, B.s_x); PUT(s_loc, B.s_loc); PUT(s_ls, B.s_ls); PUT(s_joff, B.s_joff); PUT(s_ccol, B.s_ccol);
-    PUT(imu_pre, B.imu_pre); PUT(cp_dat, B.cp_dat); PUT(pr_dat, B.pr_dat); PUT(dop_dat, B.dop_dat); PUT(sp_w, B.sp_w); PUT(gx_dat, B.gx_dat);
-    D.n_imu = (int)B.imu_gf.size(); D.n_sc = (int)B.sc_gf.size(); D.n_prior = (int)B.prior_gf.size();
-    PUT(imu_gf, B.imu_gf); PUT(sc_gf, B.sc_gf); PUT(prior_gf, B.prior_gf); D.n_idp = (int)B.idp_gf.size(); PUT(idp_gf, B.idp_gf);
-    {   // flat J v records of the scalar and the IMU factors (JtRec, swf_dev.h): the factor and its slots as the tables above hold them
-        bool fits = true;
-        auto jt_recs = [&](const std::vector<int>& list) {
-            std::vector<JtRec> out(list.size());
-            for (size_t q = 0; q < list.size(); q++) {
-                const GFac& G = B.gf[(size_t)list[q]];
-                JtRec& r = out[q];
-                r = JtRec{};
-                r.win = G.win; r.nres = G.nres; r.jld = G.jld; r.nslot = G.nslot; r.roff = G.roff; r.f = list[q];
-                if (G.nslot > JT_MAXSLOT) { fits = false; continue; }
-                for (int t = 0; t < JT_MAXSLOT; t++) {
-                    const bool has = t < G.nslot;
-                    r.joff[t] = has ? B.s_joff[(size_t)G.slot0 + t] : -1; r.loc[t] = has ? B.s_loc[(size_t)G.slot0 + t] : 0; r.ls[t] = has ? B.s_ls[(size_t)G.slot0 + t] : 0;
-                }
-            }
-            return out;
-        };
-        const std::vector<JtRec> sj = jt_recs(B.sc_gf), ij = jt_recs(B.imu_gf);
-        if (!fits) { P.release(); delete b; return fail(SWF_E_UNSUPPORTED, "scalar / IMU factor with more than JT_MAXSLOT parameter blocks"); }
-        PUT(sc_jt, sj); PUT(imu_jt, ij);
-    }
-    PUT(prior_dim, B.prior_dim); PUT(prior_Joff, B.prior_Joff); PUT(prior_roff, B.prior_roff); PUT(prior_x0off, B.prior_x0off);
-    {   // transposed copies of the prior records for the J v products
-        std::vector<double> Jt(B.prior_J.size());
-        for (size_t k = 0; k < B.prior_dim.size(); k++) {
-            const size_t n = (size_t)B.prior_dim[k]; const double* J = B.prior_J.data() + B.prior_Joff[k]; double* T = Jt.data() + B.prior_Joff[k];
-            for (size_t r = 0; r < n; r++) for (size_t c = 0; c < n; c++) T[c * n + r] = J[r * n + c];
-        }
-        PUT(prior_Jt, Jt);
-        // column -> local index of every prior record (the J v products walk the columns flat, eight at a time)
-        std::vector<int> cl(B.prior_r0.size(), -1), cc(B.prior_r0.size(), -1), pcol(B.s_ls.size(), 0), pxo(B.s_ls.size(), 0);
-        for (const GFac& G : B.gf) {
-            if (G.type != GF_PRIOR) continue;
-            int col = 0, xo = 0;
-            for (int t = 0; t < G.nslot; t++) {
-                int l = B.s_ls[G.slot0 + t], lo = B.s_loc[G.slot0 + t], mc = B.s_ccol[G.slot0 + t];
-                pcol[G.slot0 + t] = col; pxo[G.slot0 + t] = xo;
-                for (int q = 0; q < l; q++) {
-                    cl[(size_t)B.prior_roff[G.data] + col + q] = lo >= 0 ? lo + q : -1;
-                    cc[(size_t)B.prior_roff[G.data] + col + q] = mc >= 0 ? mc + q : -1;
-                }
-                col += l; xo += (l == 6 ? 7 : l);
-            }
-        }
-        PUT(prior_colloc, cl); PUT(prior_colcc, cc); PUT(s_pcol, pcol); PUT(s_pxo, pxo);
-    }
-    PUT(prior_J, B.prior_J); PUT(prior_r0, B.prior_r0); PUT(prior_x0, B.prior_x0);
-    D.n_cl = (int)B.cl.size();
-    PUT(cl, B.cl); PUT(cl_fac, B.cl_fac); PUT(cl_frow, B.cl_frow); PUT(cm_loc, B.cm_loc); PUT(cm_ls, B.cm_ls); PUT(cm_col, B.cm_col);
-    {
-        std::vector<int> cvl((size_t)std::max(B.v_tot, 1), 0);
-        for (const Clique& c : B.cl)
-            for (int m = c.mem0; m < c.mem1; m++)
-                for (int q = 0; q < B.cm_ls[(size_t)m]; q++) cvl[(size_t)c.v_off + (size_t)B.cm_col[(size_t)m] + (size_t)q] = B.cm_loc[(size_t)m] + q;
-        PUT(cv_loc, cvl);
-    }
-    D.n_pair = (int)B.pair.size();
-    PUT(pc_coff, B.pc_coff); PUT(pc_cld, B.pc_cld); PUT(pc_voff, B.pc_voff);
-    {
-        std::vector<int> pd, po, clc[5], cle;
-        for (size_t i = 0; i < B.pair.size(); i++) {
-            Pair& Pq = B.pair[i]; const WinRec& Rw = B.win[Pq.win];      // self-contained records (see Pair)
-            Pq.fsb0 = Rw.fsb0; Pq.fsb1 = Rw.fsb1; Pq.n = Rw.n_red; Pq.m = 6 * Rw.nF; Pq.S_base = Rw.S_base; Pq.P_base = Rw.P_base; Pq.q_base = (long long)6 * Rw.fr_base * GEMM_SPLIT;
-            if (b->s_direct && !Pq.is_diag && Pq.fa >= 0 && Pq.fb >= 0 && Pq.c0 == Pq.c1) continue;       // -P is already in S, nothing to add
-            (Pq.is_diag ? pd : po).push_back((int)i);
-        }
-        // off-diagonal pairs by descending entry rounds (16 entries per round): the round-2 pair-walking assembly's waves (four pairs each) become
-        // homogeneous and skip the rounds none of their pairs has; every pair is still written once, by the same arithmetic
-        std::stable_sort(po.begin(), po.end(), [&](int a, int c) {
-            return (B.pair[a].la * B.pair[a].lb + 15) / 16 > (B.pair[c].la * B.pair[c].lb + 15) / 16; });
-        for (size_t i = 0; i < B.cl.size(); i++) {
-            const Clique& c = B.cl[i];
-            if (c.d_e > 0) cle.push_back((int)i);
-            if (c.is_static) continue;
-            int d = c.d_e + c.d_f;
-            // one wavefront per clique up to 64 x 64 (three size classes); anything larger takes the workgroup kernel (class 3)
-            int cls = (c.d_e <= 1 && d <= 32 && c.n_rows <= 48) ? 0 : (c.n_rows <= 32 && d <= 48) ? 1 : (c.n_rows <= CLQ_MAXR && d <= CLQ_MAXD) ? 2 : (c.n_rows <= CLQ_TALLR && d <= 64) ? 4 : 3;
-            // latency path: every one-wavefront clique in ONE launch (the 64 x 64 instantiation; the classes differ in loop bounds and zero
-            // padding only, the sums and their order are the same: bit-identical results)
-            if (b->lat_fuse && cls < 2) cls = 2;
-            clc[cls].push_back((int)i);
-            for (int q = c.fac0; q < c.fac1; q++) if (B.gf[B.cl_fac[q]].type == GF_IMU) b->clc_imu[cls] = true;
-        }
-        D.n_pd = (int)pd.size(); D.n_po = (int)po.size(); D.n_cle = (int)cle.size();
-        {
-            // ---- assembly programs (k_assemble_flat): every pair of the two lists above, flattened into per-entry source lists with
-            // window-relative offsets; windows whose programs come out identical share one copy.  Entry order inside a window: the
-            // window's pairs in pair order, (i, j) row-major — any order would do, every entry is written by exactly one thread.
-            const int n_part = b->s_direct ? 0 : b->ls_folded ? 1 : GEMM_SPLIT, n_qpart = b->ls_folded ? 1 : GEMM_SPLIT;
-            struct Prog { std::vector<int> dst, src0, aux, src, vloc, vred, vsrc0, vi, vsrc; std::vector<unsigned> cnt, vcnt; };
-            std::vector<AsmWin> asw((size_t)n);
-            std::vector<int> t_dst, t_src0, t_aux, t_src, tv_loc, tv_red, tv_src0, tv_i, tv_src; std::vector<unsigned> t_cnt, tv_cnt;
-            std::map<std::vector<int>, std::array<int, 4>> seen;           // serialised program -> (se0, ne, ve0, nv)
-            std::vector<std::vector<int>> wpairs((size_t)n);
-            for (int i : pd) wpairs[(size_t)B.pair[i].win].push_back(i);
-            for (int i : po) wpairs[(size_t)B.pair[i].win].push_back(i);
-            bool overflow = false;
-            // the 16 x 16 tiles of S some block pair reaches, strictly below the tile diagonal (the diagonal tiles are always loaded): from
-            // EVERY pair of the window — the frame pairs whose only contribution is the -P that k_lm_schur writes straight into S have
-            // left the assembly's lists above, but their tiles are not zero
-            std::vector<unsigned> tnz((size_t)n * 4, 0u);
-            for (const Pair& Pq : B.pair) {
-                if (B.win[(size_t)Pq.win].n_red > 256) continue;
-                for (int I = Pq.ra / 16; I <= (Pq.ra + Pq.la - 1) / 16; I++)
-                    for (int J = Pq.rb / 16; J <= (Pq.rb + Pq.lb - 1) / 16 && J < I; J++) { const int t = I * (I - 1) / 2 + J; tnz[(size_t)Pq.win * 4 + (t >> 5)] |= 1u << (t & 31); }
-            }
-            for (int w = 0; w < n; w++) {
-                const WinRec& Rw = B.win[w];
-                AsmWin& A = asw[(size_t)w];
-                A.win = w; A.n_red = Rw.n_red; A.m = 6 * Rw.nF; A.loc_base = Rw.loc_base; A.S_base = Rw.S_base;
-                A.P_base = Rw.P_base * GEMM_SPLIT; A.q_base = (long long)6 * Rw.fr_base * GEMM_SPLIT;
-                A.fs_base = Rw.fsb1 > Rw.fsb0 ? B.fsb_out0[(size_t)Rw.fsb0] : 0;
-                long long Cb = -1; int vb = -1;
-                for (int c = Rw.cl0; c < Rw.cl1; c++) { if (Cb < 0 || B.cl[c].C_off < Cb) Cb = B.cl[c].C_off; if (vb < 0 || B.cl[c].v_off < vb) vb = B.cl[c].v_off; }
-                A.C_base = Cb < 0 ? 0 : Cb; A.v_base = vb < 0 ? 0 : vb;
-                Prog Pg;
-                const int nfsb = Rw.fsb1 - Rw.fsb0, mm = A.m;
-                for (int pi_ : wpairs[(size_t)w]) {
-                    const Pair& Pq = B.pair[(size_t)pi_];
-                    const bool frame_pair = Pq.fa >= 0 && Pq.fb >= 0, obs = Pq.is_diag && Pq.fa >= 0;
-                    const int ncon = Pq.c1 - Pq.c0;
-                    for (int i = 0; i < Pq.la; i++) for (int j = 0; j < Pq.lb; j++) {
-                        if (Pq.is_diag && j > i) continue;                  // lower half only; the mirror is the host's job at export
-                        const bool dg = Pq.is_diag && i == j;
-                        const int nP = frame_pair ? n_part : 0, nH = obs ? nfsb : 0;
-                        if (ncon > 4095 || nH > 4095) overflow = true;
-                        Pg.dst.push_back((Pq.ra + i) * Pq.n + Pq.rb + j);
-                        Pg.cnt.push_back((unsigned)ncon | ((unsigned)nP << 12) | ((unsigned)nH << 17) | ((dg ? 1u : 0u) << 29) | ((frame_pair && b->s_direct ? 1u : 0u) << 30));
-                        Pg.src0.push_back((int)Pg.src.size());
-                        Pg.aux.push_back(dg ? (Pq.loc_a - Rw.loc_base) + i : 0);
-                        for (int c = Pq.c0; c < Pq.c1; c++) Pg.src.push_back((int)(B.pc_coff[(size_t)c] + (long long)i * B.pc_cld[(size_t)c] + j - A.C_base));
-                        if (nP) {
-                            const int pr = 6 * Pq.fa + i, pc = 6 * Pq.fb + j;
-                            const long long pel = pr >= pc ? (long long)pr * mm + pc : (long long)pc * mm + pr;
-                            for (int q = 0; q < nP; q++) Pg.src.push_back((int)((long long)q * mm * mm + pel));
-                        }
-                        if (nH) {
-                            const int hi = i > j ? i : j, lo = i > j ? j : i;
-                            for (int k2 = Rw.fsb0; k2 < Rw.fsb1; k2++) Pg.src.push_back((B.fsb_out0[(size_t)k2] - A.fs_base + Pq.fa) * FS_VAL + hi * (hi + 1) / 2 + lo);
-                        }
-                        if (dg) for (int c = Pq.c0; c < Pq.c1; c++) Pg.src.push_back(B.pc_voff[(size_t)c] + i - A.v_base);
-                    }
-                    if (!Pq.is_diag) continue;
-                    for (int i = 0; i < Pq.la; i++) {
-                        const int nH = obs ? nfsb : 0, nQ = obs ? n_qpart : 0;
-                        Pg.vloc.push_back(Pq.loc_a - Rw.loc_base + i); Pg.vred.push_back(Pq.ra + i); Pg.vi.push_back(obs ? i : 0);
-                        Pg.vcnt.push_back((unsigned)ncon | ((unsigned)nQ << 12) | ((unsigned)nH << 17));
-                        Pg.vsrc0.push_back((int)Pg.vsrc.size());
-                        if (nH) for (int k2 = Rw.fsb0; k2 < Rw.fsb1; k2++) Pg.vsrc.push_back((B.fsb_out0[(size_t)k2] - A.fs_base + Pq.fa) * FS_VAL);
-                        for (int c = Pq.c0; c < Pq.c1; c++) Pg.vsrc.push_back(B.pc_voff[(size_t)c] + i - A.v_base);
-                        for (int q = 0; q < nQ; q++) Pg.vsrc.push_back(q * mm + 6 * Pq.fa + i);
-                    }
-                }
-                // serialise and look up
-                std::vector<int> key;
-                key.reserve(Pg.dst.size() * 4 + Pg.src.size() + Pg.vloc.size() * 5 + Pg.vsrc.size() + 8);
-                key.push_back((int)Pg.dst.size()); key.push_back((int)Pg.vloc.size());
-                key.insert(key.end(), Pg.dst.begin(), Pg.dst.end()); for (unsigned c : Pg.cnt) key.push_back((int)c);
-                key.insert(key.end(), Pg.src0.begin(), Pg.src0.end()); key.insert(key.end(), Pg.aux.begin(), Pg.aux.end()); key.insert(key.end(), Pg.src.begin(), Pg.src.end());
-                key.insert(key.end(), Pg.vloc.begin(), Pg.vloc.end()); key.insert(key.end(), Pg.vred.begin(), Pg.vred.end()); for (unsigned c : Pg.vcnt) key.push_back((int)c);
-                key.insert(key.end(), Pg.vsrc0.begin(), Pg.vsrc0.end()); key.insert(key.end(), Pg.vi.begin(), Pg.vi.end()); key.insert(key.end(), Pg.vsrc.begin(), Pg.vsrc.end());
-                auto it = seen.find(key);
-                if (it == seen.end()) {
-                    const int se0 = (int)t_dst.size(), ve0 = (int)tv_loc.size(), so = (int)t_src.size(), vo = (int)tv_src.size();
-                    t_dst.insert(t_dst.end(), Pg.dst.begin(), Pg.dst.end()); t_cnt.insert(t_cnt.end(), Pg.cnt.begin(), Pg.cnt.end()); t_aux.insert(t_aux.end(), Pg.aux.begin(), Pg.aux.end());
-                    for (int x : Pg.src0) t_src0.push_back(x + so);
-                    t_src.insert(t_src.end(), Pg.src.begin(), Pg.src.end());
-                    tv_loc.insert(tv_loc.end(), Pg.vloc.begin(), Pg.vloc.end()); tv_red.insert(tv_red.end(), Pg.vred.begin(), Pg.vred.end()); tv_cnt.insert(tv_cnt.end(), Pg.vcnt.begin(), Pg.vcnt.end());
-                    tv_i.insert(tv_i.end(), Pg.vi.begin(), Pg.vi.end());
-                    for (int x : Pg.vsrc0) tv_src0.push_back(x + vo);
-                    tv_src.insert(tv_src.end(), Pg.vsrc.begin(), Pg.vsrc.end());
-                    it = seen.emplace(std::move(key), std::array<int, 4>{ se0, (int)Pg.dst.size(), ve0, (int)Pg.vloc.size() }).first;
-                }
-                A.se0 = it->second[0]; A.ne = it->second[1]; A.ve0 = it->second[2]; A.nv = it->second[3];
-                D.as_max_ne = std::max(D.as_max_ne, A.ne); D.as_max_nv = std::max(D.as_max_nv, A.nv);
-            }
-            if (overflow) { P.release(); delete b; return fail(SWF_E_UNSUPPORTED, "assembly program: more than 4095 contributions to one entry of the reduced system"); }
-            b->asm_programs = (int)seen.size();
-            auto nonempty_i = [](std::vector<int>& v) { if (v.empty()) v.push_back(0); };
-            auto nonempty_u = [](std::vector<unsigned>& v) { if (v.empty()) v.push_back(0u); };
-            nonempty_i(t_dst); nonempty_u(t_cnt); nonempty_i(t_src0); nonempty_i(t_aux); nonempty_i(t_src);
-            nonempty_i(tv_loc); nonempty_i(tv_red); nonempty_u(tv_cnt); nonempty_i(tv_src0); nonempty_i(tv_i); nonempty_i(tv_src);
-            PUT(asw, asw); PUT(s_tnz, tnz);
-            D.rr_nmax = b->rr_nmax;
-            PUT(as_dst, t_dst); PUT(as_cnt, t_cnt); PUT(as_src0, t_src0); PUT(as_aux, t_aux); PUT(as_src, t_src);
-            PUT(av_loc, tv_loc); PUT(av_red, tv_red); PUT(av_cnt, tv_cnt); PUT(av_src0, tv_src0); PUT(av_i, tv_i); PUT(av_src, tv_src);
-        }
-        {
-            std::vector<Pair> vd, vo;
-            for (int i : pd) vd.push_back(B.pair[i]);
-            for (int i : po) vo.push_back(B.pair[i]);
-            PUT(pair_d, vd); PUT(pair_o, vo);
-        }
-        {
-            std::vector<Clique> v;
-            for (int i : cle) v.push_back(B.cl[i]);
-            PUT(cle_rec, v);
-            for (int k = 0; k < 5; k++) {
-                v.clear();
-                for (int i : clc[k]) v.push_back(B.cl[i]);
-                D.n_clc[k] = (int)clc[k].size(); rc |= P.put(v, &D.clc_rec[k]);
-            }
-        }
-    }
-#undef PUT
-    // mutable buffers
     rc |= P.zeros(B.n_x, &D.x); rc |= P.zeros(B.n_x, &D.xc); rc |= P.zeros(B.n_x, &D.x0);
     rc |= P.zeros(B.n_loc, &D.g); rc |= P.zeros(B.n_loc, &D.diag); rc |= P.zeros(B.n_loc, &D.rhs); rc |= P.zeros(B.n_loc, &D.vc);
     rc |= P.zeros(B.n_loc, &D.y); rc |= P.zeros(B.n_loc, &D.step);
     rc |= P.zeros(B.S_tot, &D.S); rc |= P.zeros(B.Lt_tot, &D.L);
-    if (b->max_red > b->rr_nmax && b->max_red <= CB_NMAX) rc |= P.zeros((size_t)n * (CB_MAXT - 1) * 256, &D.Linv);
-    // few windows, one of them on the streamed Cholesky: the factorisation is spread over the chip, two tile columns per launch (k_chol_col)
-    if (b->max_red > b->rr_nmax && b->max_red <= CC_NMAX && n * 4 <= b->n_cu && !getenv("SWF_NO_CHOL_COL")) rc |= P.zeros(B.Lt_tot, &D.Wk);      // >= 4 workgroups per window
+    if (B.want_Linv) rc |= P.zeros((size_t)n * (CB_MAXT - 1) * 256, &D.Linv);
+    if (B.want_Wk) rc |= P.zeros(B.Lt_tot, &D.Wk);
     rc |= P.zeros((size_t)n, &D.ws); rc |= P.zeros((size_t)n, &b->ws_alt); rc |= P.zeros((size_t)n, &b->ws_alt2); rc |= P.zeros((size_t)n * SWF_MAX_TRACE, &D.trace);
     b->ws_primary = D.ws;
     size_t np = (size_t)D.n_proj;
@@ -1330,64 +392,24 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
     rc |= P.zeros((size_t)std::max(1, 6 * B.n_fr) * GEMM_SPLIT, &D.lmq);
     rc |= P.zeros((size_t)B.r_tot, &D.g_r); rc |= P.zeros((size_t)B.j_tot, &D.g_J);
     rc |= P.zeros((size_t)D.n_gf, &D.g_cost); rc |= P.zeros((size_t)D.n_gf, &D.g_aux);
-    {
-        const double* ci = nullptr; const double* di = nullptr;
-        B.C_init.resize((size_t)B.C_tot, 0.0); B.dgraw_init.resize((size_t)B.v_tot, 0.0);
-        rc |= P.put(B.C_init, &ci); rc |= P.put(B.dgraw_init, &di);
-        D.C = (double*)ci; D.cv_dgraw = (double*)di;
-    }
     rc |= P.zeros((size_t)B.v_tot, &D.cv_graw); rc |= P.zeros((size_t)B.v_tot, &D.cv_cs);
     rc |= P.zeros((size_t)B.e_tot, &D.cE);
-    // composite IMU-GNSS factors: operator arguments over the whole batch + where each factor's prior record and clique live
-    b->n_comp = (int)B.co_M.size();
-    if (b->n_comp) {
-        const int nc = b->n_comp;
-        std::vector<int> eo(nc + 1, 0), no(nc + 1, 0), roff(nc), x0off(nc), voff(nc);
-        std::vector<long long> pno(nc + 1, 0), nno(nc + 1, 0), go(nc + 1, 0), g2o(nc + 1, 0), Joff(nc), Coff(nc);
-        for (int f = 0; f < nc; f++) {
-            const int M = B.co_M[f], N = B.co_N[f], G = 30 + N;
-            b->comp_nmax = std::max(b->comp_nmax, N); b->comp_nmin = std::min(b->comp_nmin, N);
-            eo[f + 1] = eo[f] + M; no[f + 1] = no[f] + N; pno[f + 1] = pno[f] + 15LL * M * N; nno[f + 1] = nno[f] + (long long)N * N;
-            go[f + 1] = go[f] + G; g2o[f + 1] = g2o[f] + (long long)G * G;
-            const GFac& Gf = B.gf[B.co_gf[f]];
-            const Clique& Cq = B.cl[Gf.clique];
-            // either its own static clique (every block outside group 0: k_comp_scatter writes C = H and the diagonal there), or a member of
-            // the clique of the ONE group-0 block it touches (its rows reach the elimination through the clique's Jacobian: Coff = -1)
-            if (Cq.is_static ? (Cq.d_f != G || Cq.d_e != 0) : (Cq.d_e <= 0)) { P.release(); delete b; return fail(SWF_E_UNSUPPORTED, "composite factor: its blocks must all be variable"); }
-            Joff[f] = B.prior_Joff[Gf.data]; roff[f] = B.prior_roff[Gf.data]; x0off[f] = B.prior_x0off[Gf.data];
-            Coff[f] = Cq.is_static ? Cq.C_off : -1; voff[f] = Cq.is_static ? Cq.v_off : -1;
-        }
-        b->comp_ne = eo[nc];
-        CompArgs& A = b->CA; CompMeta& Mt = b->CM;
-        A.n = nc; A.want_jac = 1;
-        rc |= P.put(B.co_M, &A.M); rc |= P.put(B.co_N, &A.N); rc |= P.put(eo, &A.e_off); rc |= P.put(no, &A.n_off);
-        rc |= P.put(pno, &A.pn_off); rc |= P.put(nno, &A.nn_off); rc |= P.put(go, &A.g_off); rc |= P.put(g2o, &A.g2_off);
-        { const double* t1 = nullptr; const double* t2 = nullptr; rc |= P.put(B.co_pose, &t1); rc |= P.put(B.co_sb, &t2); A.pose = (double*)t1; A.sb = (double*)t2; }
-        { const double* t1 = nullptr; const double* t2 = nullptr; rc |= P.put(B.co_pose, &t1); rc |= P.put(B.co_sb, &t2); b->co_pose0 = (double*)t1; b->co_sb0 = (double*)t2; }
-        rc |= P.put(B.co_pose_lin, &A.pose_lin); rc |= P.put(B.co_sb_lin, &A.sb_lin); rc |= P.put(B.co_Hpp, &A.Hpp); rc |= P.put(B.co_HpN, &A.HpN);
-        rc |= P.put(B.co_rhs_p, &A.rhs_p); rc |= P.put(B.co_HNN, &A.HNN); rc |= P.put(B.co_rhsN, &A.rhsN); rc |= P.put(B.co_pre, &A.pre); rc |= P.put(B.co_pbgw, &A.pbgw);
-        rc |= P.put(B.co_mid, &A.mid); rc |= P.put(B.co_H12, &A.H12);
-        rc |= P.zeros((size_t)eo[nc] * 225, &A.hmn_inv); rc |= P.zeros((size_t)eo[nc] * 225, &A.hmn_2); rc |= P.zeros((size_t)eo[nc] * 225, &A.hmn_0);
-        rc |= P.zeros((size_t)pno[nc], &A.hmn_N); rc |= P.zeros((size_t)eo[nc] * 15, &A.rhsmn);
-        rc |= P.zeros((size_t)g2o[nc], &A.Hd); rc |= P.zeros((size_t)go[nc], &A.rd); rc |= P.zeros((size_t)g2o[nc], &A.Ld); rc |= P.zeros((size_t)go[nc], &A.r0);
-        rc |= P.zeros((size_t)nc * 32, &A.old); rc |= P.zeros((size_t)no[nc], &A.N_old); rc |= P.zeros((size_t)nc, &A.history); rc |= P.zeros((size_t)nc, &A.status);
-        rc |= P.zeros((size_t)nc * 32, &Mt.outer); rc |= P.zeros((size_t)no[nc], &Mt.Nv); rc |= P.zeros((size_t)nc, &Mt.active);
+    if (nc) {
+        const size_t ne = (size_t)B.co_eo[nc], nn = (size_t)B.co_no[nc], ng = (size_t)B.co_go[nc], ng2 = (size_t)B.co_g2o[nc];
+        rc |= P.zeros(ne * 225, &A.hmn_inv); rc |= P.zeros(ne * 225, &A.hmn_2); rc |= P.zeros(ne * 225, &A.hmn_0);
+        rc |= P.zeros((size_t)B.co_pno[nc], &A.hmn_N); rc |= P.zeros(ne * 15, &A.rhsmn);
+        rc |= P.zeros(ng2, &A.Hd); rc |= P.zeros(ng, &A.rd); rc |= P.zeros(ng2, &A.Ld); rc |= P.zeros(ng, &A.r0);
+        rc |= P.zeros((size_t)nc * 32, &A.old); rc |= P.zeros(nn, &A.N_old); rc |= P.zeros((size_t)nc, &A.history); rc |= P.zeros((size_t)nc, &A.status);
+        rc |= P.zeros((size_t)nc * 32, &Mt.outer); rc |= P.zeros(nn, &Mt.Nv); rc |= P.zeros((size_t)nc, &Mt.active);
         A.outer = Mt.outer; A.Nv = Mt.Nv; A.active = Mt.active;
-        rc |= P.zeros((size_t)go[nc], &A.res_out); rc |= P.zeros((size_t)g2o[nc], &A.jac_out);
-        rc |= P.zeros((size_t)(eo[nc] + nc) * 450, &A.Jw); rc |= P.zeros((size_t)(eo[nc] + nc) * 16, &A.rw);
-        {
-            std::vector<int> qf, qk;
-            for (int f = 0; f < nc; f++) for (int k = 0; k <= B.co_M[f]; k++) { qf.push_back(f); qk.push_back(k); }
-            A.n_iq = (int)qf.size();
-            rc |= P.put(qf, &A.iq_f); rc |= P.put(qk, &A.iq_k); rc |= P.zeros((size_t)nc, &A.todo);
-        }
-        rc |= P.put(B.co_win, &Mt.win); rc |= P.put(B.co_xo_off, &Mt.xo_off); rc |= P.put(B.co_xo, &Mt.xo);
-        rc |= P.put(Joff, &Mt.Joff); rc |= P.put(roff, &Mt.roff); rc |= P.put(x0off, &Mt.x0off); rc |= P.put(Coff, &Mt.Coff); rc |= P.put(voff, &Mt.voff);
-        Mt.prior_J = (double*)D.prior_J; Mt.prior_Jt = (double*)D.prior_Jt; Mt.prior_r0 = (double*)D.prior_r0; Mt.prior_x0 = (double*)D.prior_x0;
+        rc |= P.zeros(ng, &A.res_out); rc |= P.zeros(ng2, &A.jac_out);
+        rc |= P.zeros((ne + nc) * 450, &A.Jw); rc |= P.zeros((ne + nc) * 16, &A.rw);
+        rc |= P.zeros((size_t)nc, &A.todo);
     }
     if (!rc) rc = P.flush();
-    if (rc) { P.release(); delete b; return fail(SWF_E_NODEVICE, "device allocation / upload failed"); }
-    *out = b;
+    if (rc) { P.release(); return fail(SWF_E_NODEVICE, "device allocation / upload failed"); }
+    b->win = std::move(B.win); b->hw = std::move(B.hw);      // the host's copy of the window records, and what it keeps per window
+    *out = owner.release();
     int urc = swf_batch_upload_state(b);
     if (urc != SWF_OK) { swf_batch_destroy(b); *out = nullptr; return urc; }
     return SWF_OK;
@@ -2595,6 +1617,37 @@ extern "C" int swf_batch_export_jacobian(swf_batch* b, int32_t w, double* r, dou
     }
     if (!ok) return fail(SWF_E_NODEVICE, "download failed");
     return SWF_OK;
+}
+
+// The symbolic phase alone, with no device: plan_build + plan_validate for the given chip size and launch-shape knobs (flags: 1 =
+// SWF_NO_LAT_FUSE, 2 = SWF_NO_CHOL_COL); the validator's finding is left in swf_last_error.  corrupt_table 1 .. 7 damages entry
+// corrupt_index of as_src / sch_rec / s_tnz / prior_colloc / loc2x / co_voff / pair_o in this call's own plan before it is validated (the negative control of the validator).
+// info (may be null), 12 ints: ls_var, ls_qpb, ls_gqpb, ls_folded, lat_fuse, want_aux, want_Linv, want_Wk, asm_programs, n_pch_split, max_red, n_pch.
+extern "C" int swf_debug_plan_check(const swf_flat_window* const* windows, int32_t n, int32_t n_cu, int32_t ls_variant, int32_t ls_qpb, int32_t ls_grad_qpb,
+                                    int32_t flags, int32_t corrupt_table, int32_t corrupt_index, int32_t* info) {
+    if (!windows || n <= 0 || n_cu <= 0) return fail(SWF_E_INVALID, "swf_debug_plan_check: bad arguments");
+    PlanShape sh;
+    sh.n_cu = n_cu; sh.ls_variant = ls_variant; sh.ls_qpb = ls_qpb; sh.ls_grad_qpb = ls_grad_qpb; sh.no_lat_fuse = flags & 1; sh.no_chol_col = flags & 2;
+    Plan B; std::string err;
+    int rc = plan_build(windows, n, sh, B, err);
+    if (rc != SWF_OK) return fail(rc, err);
+    if (corrupt_table) {
+        const size_t i = (size_t)corrupt_index;
+        if (corrupt_table == 1 && i < B.as_src.size()) B.as_src[i] += 1 << 28;
+        else if (corrupt_table == 2 && i < B.sch_rec.size()) B.sch_rec[i] ^= 1;
+        else if (corrupt_table == 3 && i < B.s_tnz.size() && B.s_tnz[i]) B.s_tnz[i] &= B.s_tnz[i] - 1;      // its lowest set bit
+        else if (corrupt_table == 4 && i < B.prior_colloc.size()) B.prior_colloc[i] ^= 1;
+        else if (corrupt_table == 5 && i < B.loc2x.size()) B.loc2x[i] ^= 1;
+        else if (corrupt_table == 6 && i < B.co_voff.size()) B.co_voff[i] += 1 << 28;
+        else if (corrupt_table == 7 && i < B.pair_o.size()) B.pair_o[i].q_base += 8;
+        else return fail(SWF_E_INVALID, "swf_debug_plan_check: nothing to corrupt there");
+    }
+    if (info) {
+        const int v[12] = { B.ls_var, B.ls_qpb, B.ls_gqpb, B.ls_folded, B.lat_fuse, B.want_aux, B.want_Linv, B.want_Wk, B.asm_programs, B.n_pch_split, B.max_red, B.n_pch };
+        for (int k = 0; k < 12; k++) info[k] = v[k];
+    }
+    rc = plan_validate(B, err);
+    return rc == SWF_OK ? SWF_OK : fail(rc, err);
 }
 
 #ifdef SWF_PROFILE_CHOL

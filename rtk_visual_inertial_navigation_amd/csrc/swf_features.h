@@ -11,16 +11,11 @@
 #include <string>
 #include <vector>
 #include "../../include/swf_solver.h"
+// FeatWinSrc, the window's visual factors as the caller gave them, is declared in swf_plan.h: the symbolic phase fills it (HostWin::feat)
+// and that file must stay free of HIP, which this header is not; swf_internal_feature_tables below is its only reader
+#include "swf_plan.h"
 
 enum { FEAT_BLK = 256 };      // observations per workgroup (whole features; a longer track has a workgroup of its own)
-
-// what the symbolic phase keeps of one window (copied at swf_batch_create: the caller's arrays are read during that call only)
-struct FeatWinSrc {
-    int x_base = 0, n_pose = 0, n_sb = 0, n_lm = 0, n_sc = 0;
-    std::vector<int> proj_idx; std::vector<double> proj_uv;                             // [n_proj][3], [n_proj][2]
-    std::vector<int> idp_kind, idp_idx; std::vector<double> idp_pts;                    // [n_idp], [n_idp][5], [n_idp][6]
-    double pbg[3] = { 0, 0, 0 }; double sqrt_info = 0;
-};
 
 // host form of the tables (concatenated over the windows of a batch)
 struct FeatTables {

@@ -673,8 +673,6 @@ __global__ void __launch_bounds__(128) k_eval_idp(DevBatch B) {
 // =========================================================================================
 // (prior_block_dx, the dx of one kept block, lives in swf_dev.h: the fix-and-hold operator evaluates the prior with it too)
 #define PRIOR_LDS_DIM 512               // priors up to this dimension ride as a segment of the fused evaluation grids
-#define PRIOR_SPLIT_DIM 96              // priors beyond this dimension are evaluated in row chunks, a workgroup each
-#define PRIOR_CHUNK 32
 template <bool JAC>
 __device__ __forceinline__ void d_eval_prior(const DevBatch& B, int blk, double* sm) {      // sm: dx[n] | r[n] | red[16]
     if (blk >= B.n_pch) return;
@@ -870,7 +868,7 @@ __device__ __forceinline__ double gf_row_term(const DevBatch& B, int roff, int k
 }
 template <int MODE>
 __device__ __forceinline__ double gf_row_term(const DevBatch& B, const GFac& G, int k, double a) { return gf_row_term<MODE>(B, G.roff, k, a); }
-// Row k of (J v) for a scalar or an IMU factor, from the factor's flat record (JtRec, swf_dev.h: the host built it from the GFac and
+// Row k of (J v) for a scalar or an IMU factor, from the factor's flat record (JtRec, swf_records.h: the host built it from the GFac and
 // its slots, so the addressing is ONE load level deep instead of sc_gf -> gf -> slot arrays).  The factor's columns are walked flat,
 // slot after slot (a slot without a Jacobian block takes no columns), CH at a time: every Jacobian element and every vector entry
 // of the round is requested unconditionally, the columns beyond the factor's last clamped to element 0, before the first is used.
@@ -1003,8 +1001,6 @@ __device__ __forceinline__ void d_jtimes_prior(const DevBatch& B, const DevOpt& 
 //   C = M_ff - M_fe Einv M_ef,  graw = J_f^T r,  dgraw = diag(M_ff),  cs = -M_fe Einv g_e
 // for k_assemble, plus Einv / M_ef / g_e for the back-substitution.
 // =========================================================================================
-#define CLQ_MAXD 64
-#define CLQ_MAXR 64
 #ifdef SWF_PROFILE_CLQ
 __device__ unsigned long long g_clq_stamps[16];
 #ifndef SWF_PROFILE_CLQ_IDX
@@ -1293,7 +1289,6 @@ __global__ void __launch_bounds__(256) k_clique_elim4(DevBatch B, DevOpt O) { d_
 // class 4: up to 96 rows x 64 columns — the clique of a speed-bias block that two composite IMU-GNSS factors touch (the reference's own
 // ordering puts every other speed-bias block into group 0, R/swf/swf_gnss.cpp:683-691: 2 x (30 + N) rows, 9 + 6 + 9 + 6 + 6 + 9 + N
 // columns: N <= 18 ambiguities fit 96 rows x 64 columns, more take k_clique_big).  The four-wave form of the same function.
-#define CLQ_TALLR 96
 template <bool GRAD = false>
 __global__ void __launch_bounds__(256) k_clique_tall(DevBatch B, DevOpt O) { d_clique_elim<CLQ_TALLR, 64, 9, 4, 8, 4, 4, GRAD>(B, O, (int)blockIdx.x); }
 
@@ -1329,8 +1324,6 @@ __global__ void __launch_bounds__(LS_NT(NCW, TW)) k_lm_clique(DevBatch B, DevOpt
 //   thread j:       column j of T = Einv M_ef
 //   thread (i, j):  C_ij = J_i . J_j - M_ei . T_j over the lower triangle
 // =========================================================================================
-#define CB_MAXD 768                           // columns of a big clique (d_e + d_f)
-#define CB_MAXED 1536                         // d_e x (d_e + d_f) of a big clique: the rows of M that belong to e, and T = Einv M_ef, live in LDS
 #define CB_LDS_J 12288                        // doubles of Jacobian staged in LDS (96 KB); larger ones are read through L2
 #define CB_NT 1024
 // Round 5: rewritten for the cliques the reference's RTK topology produces with more than 18 ambiguities (two composite factors on an
@@ -1502,8 +1495,6 @@ __global__ void __launch_bounds__(CB_NT) k_clique_big2(DevBatch B, DevOpt O) {
 //   27 doubles = lower(Jp^T Jp)(21) | Jp^T r (6);   k_assemble<true> adds the blocks in order.  (The landmark part of the
 //   reduced right-hand side, sum Y g_l per frame, comes out of k_lm_schur's matrix-core pass: DevBatch::lmq.)
 // =========================================================================================
-#define FS_BLK 256
-#define FS_VAL 27
 #define FS_HALF 14                            // values staged per pass
 // The same, fused into the Jacobian evaluation (k_eval_ps<true>, one workgroup per frame-sum block): thread t evaluates observation t of
 // the block and the 27 products never leave the chip — Jp and r are not read back (112 B per observation and one launch less).

@@ -361,9 +361,8 @@ __device__ __forceinline__ bool chol_pivot_tile(double (*D)[17], double (*LiJ)[1
 //          4 MFMAs with the panel operands from LDS, store; the next tile's loads are issued before the MFMAs].
 // Step 0 reads S (lower; diagonal tiles mirrored), later steps read the L buffer.  Right-looking backward pass.
 // =========================================================================================
-#define CB_NMAX 640                     // largest reduced system of the tiled kernels (hs_row reaches ~620 in a live window)
+// (CB_NMAX, CC_NMAX: swf_records.h, shared with the symbolic phase)
 #define CB_MAXT (CB_NMAX / 16 + 1)      // tile rows: 40 of the matrix + the rhs row
-#define CC_NMAX 512                     // k_chol_col keeps two panels in LDS: up to 512 dimensions
 #define CC_MAXT (CC_NMAX / 16 + 1)
 template <bool BACK_ONLY>
 __global__ void __launch_bounds__(1024) k_chol_big(DevBatch B) {
@@ -1063,7 +1062,7 @@ __device__ unsigned long long g_dog_stamps[16];
 // threads of the per-window control kernels k_dogleg / k_decide: their loops over the window's dimensions and cost terms are chains of
 // dependent loads, so a window's latency falls with the thread count (one window: k_dogleg 20.7 -> ? us); the same count for every
 // batch size, because the order of the strided partial sums depends on it
-#define CTL_NT 256
+// (CTL_NT: swf_records.h, shared with the symbolic phase)
 // Latency notes (one window: 46 k cycles in round 3, most of them chains of dependent loads — block table -> offsets -> values, three
 // blocks per thread one after the other, twice): the passes below run over FLAT host-built tables instead.  loc2x[i] = ambient
 // coordinate of local dimension i (-1 for the six dimensions of a pose block, which a thread per pose block handles with Plus);

@@ -15,8 +15,6 @@
 #pragma once
 #include "swf_kernels.h"
 
-#define CO_MAXN 64                         // ambiguities per composite factor (the reference's data model: 3 constellations x NFREQ 2 on up to MAXOBS 64
-                                           // satellites, R/gnss/include/common_function.h:24-37; 30..48 per gap is a normal open-sky epoch)
 #define CO_TINYN 12                        // batches: a third instantiation for <= 12 ambiguities (25 KB of LDS and 84 registers: six workgroups per CU; the chain of a factor is latency-bound, so what a batch gains is factors in flight)
 #define CO_SMALLN 24                       // k_comp_elim / k_comp_eigroot are instantiated for <= 24 (36 KB of LDS, four workgroups per CU) and <= 64 ambiguities
 #define CO_MAXG (30 + CO_MAXN)

@@ -35,8 +35,7 @@
 // Per observation the kernel reads 160 B (Jp, Jl, r) and writes nothing; per landmark it writes Einv, g_l (back-substitution).
 #pragma once
 typedef double double4_t __attribute__((ext_vector_type(4)));
-#define GEMM_SPLIT 16                         // fixed landmark split: partial products P_0..P_15, summed in order (by k_lm_schur
-                                              // itself when one block covers them all, else by k_assemble)
+// (GEMM_SPLIT, LS_GRAD_QPB, LS_NB, LS_MAXF: swf_records.h, shared with the symbolic phase)
 #ifdef SWF_PROFILE_GEMM
 __device__ unsigned long long g_gemm_stamps[16];
 #define GSTAMP_ACC(i, t0) do { if (bx_ == 0 && by_ == 0 && (threadIdx.x & 63) == 0) g_gemm_stamps[i] += __builtin_amdgcn_s_memtime() - (t0); } while (0)
@@ -45,10 +44,7 @@ __device__ unsigned long long g_gemm_stamps[16];
 #define GSTAMP_ACC(i, t0)
 #define GNOW() 0ULL
 #endif
-#define LS_GRAD_QPB 4                         // landmark parts per workgroup of the gradient-only pass (GRAD below) in batches
-#define LS_NB 4                               // ring buffers = producer teams
 #define LS_NT(NCW, TW) ((LS_NB * (TW) + (NCW)) * 64)
-#define LS_MAXF 64                            // observing frames per window (64-bit frame masks)
 #define LS_SPIN_MAX (1 << 22)                 // bound of the hand-off polls (a broken table must not hang the device)
 // size classes (LDR = doubles per panel column, = 16 mod 32: the four k-slots of an operand read fall on distinct banks):
 //   <8, 2, 2,  80>   <= 10 frames  (<= 10 tiles)            <8, 5, 2, 144>   <= 21 frames (<= 36 tiles)
@@ -122,7 +118,7 @@ __device__ __forceinline__ void d_lm_schur(const DevBatch& B, const DevOpt& O, i
             while (tr * (tr + 1) / 2 <= u) tr++;
             tc = u - tr * (tr - 1) / 2;
         };
-        constexpr bool CAN_FOLD = TPW <= 5 && NCW == 8;     // these blocks have the registers for the folded product
+        constexpr bool CAN_FOLD = ls_can_fold(NCW, TPW);     // these blocks have the registers for the folded product (swf_records.h: the plan decides ls_folded by the same predicate)
         constexpr int NDS = LDR <= 144 ? 1 : 2;             // slots that can hold a diagonal tile (the list's first nt entries over NCW waves)
         double4_t acc[TPW], tot[CAN_FOLD ? TPW : 1];
         double qa[NDS], qt[NDS];

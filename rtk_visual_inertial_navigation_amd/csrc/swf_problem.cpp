@@ -8,7 +8,6 @@
 // to its residual blocks (R/factor/gnss_imu_factor.cpp:110-113), blocks that no enabled residual
 // block touches are left out of the solve (ceres removes unused blocks from the reduced program),
 // failures surface through the return code AND summary.termination.
-#include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
 #include <cstdio>

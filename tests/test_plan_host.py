@@ -1,0 +1,202 @@
+"""The symbolic phase on the CPU (csrc/swf_plan.cpp through swf_debug_plan_check: plan_build + plan_validate, no device): windows of
+every kind the GPU tier solves must validate at a full-size and at a tiny chip, the rejections keep their codes and messages, a
+damaged table is reported (the validator's negative control), and a stand-alone program runs the same code under the address and
+undefined-behaviour sanitizers."""
+import ctypes
+import glob
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import cfg5_marg_gen
+import composite_gen
+import rtk_topology_gen as rt
+from rtk_visual_inertial_navigation_amd import build, solver, synth
+from rtk_visual_inertial_navigation_amd.flat import FlatWindowC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_INVALID, E_UNSUPPORTED = -2, -3
+INFO = ("ls_var", "ls_qpb", "ls_gqpb", "ls_folded", "lat_fuse", "want_aux", "want_Linv", "want_Wk", "asm_programs", "n_pch_split", "max_red", "n_pch")
+
+
+def plan_check(wins, n_cu=256, ls_variant=0, ls_qpb=0, ls_grad_qpb=0, flags=0, corrupt=(0, 0)):
+    """(return code, swf_last_error, info) of swf_debug_plan_check on the windows."""
+    build.build()
+    lib = ctypes.CDLL(solver.LIB_PATH)
+    lib.swf_last_error.restype = ctypes.c_char_p
+    cs = [w.c_struct() for w in wins]
+    arr = (ctypes.POINTER(FlatWindowC) * len(cs))(*[ctypes.pointer(c) for c in cs])
+    info = (ctypes.c_int32 * len(INFO))()
+    rc = lib.swf_debug_plan_check(arr, ctypes.c_int32(len(cs)), ctypes.c_int32(n_cu), ctypes.c_int32(ls_variant), ctypes.c_int32(ls_qpb),
+                                  ctypes.c_int32(ls_grad_qpb), ctypes.c_int32(flags), ctypes.c_int32(corrupt[0]), ctypes.c_int32(corrupt[1]), info)
+    return rc, (lib.swf_last_error() or b"").decode(), dict(zip(INFO, info))
+
+
+def _golden():
+    from golden.make_golden import load_case
+    return [(os.path.basename(f)[:-4], load_case(f)[0]) for f in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "*.npz")))]
+
+
+def _big_prior_window():
+    """A slid window whose linear prior is larger than PRIOR_SPLIT_DIM (96) rows: evaluated in row chunks.  The prior's values are
+    arbitrary (a plan depends on structure only)."""
+    full = cfg5_marg_gen.make_full((17, 40, 4, 21))
+    _, head = cfg5_marg_gen.marginalisation_window(full)
+    g, l = full.block_sizes()
+    dim = int(sum(l[b] for b in head))
+    rng = np.random.default_rng(5)
+    return cfg5_marg_gen.slid_window(full, head, np.triu(rng.normal(0, 1, (dim, dim))) + 3 * np.eye(dim), rng.normal(0, 1, dim))
+
+
+def _rtk_composite_window():
+    wx, vis, hid = rt.explicit_window(K_vis=3, M=4, F=16, S=5, seed=11)
+    ews, kept = rt.epoch_windows(wx)
+    rng = np.random.default_rng(3)
+    pri = []
+    for e in kept:                                            # stand-ins for the per-epoch GNSS priors, of the right shapes
+        n = sum(6 if s == 7 else s for s, _ in e)
+        G = rng.normal(0, 1, (n + 3, n)); pri.append(dict(A=G.T @ G, b=rng.normal(0, 1, n)))
+    M, K = wx.meta["M"], wx.meta["K_vis"]
+    return wx, rt.composite_window(wx, [rt.assemble_np(M, kept[g * M:(g + 1) * M], pri[g * M:(g + 1) * M]) for g in range(K - 1)])
+
+
+def _valid_windows():
+    out = _golden()
+    out += [("synth cfg3 default K6 F10", synth.make_window(3, K=6, F=10, S=3, seed=1)), ("synth cfg3 K4 F6", synth.make_window(3, K=4, F=6, S=2, seed=2)),
+            ("synth cfg2 K3 F5", synth.make_window(2, K=3, F=5, S=0, seed=3))]
+    wx, wc = _rtk_composite_window()
+    out += [("rtk explicit", wx), ("rtk composite", wc)]
+    rng = np.random.default_rng(1)
+    out += [("composite", composite_gen.make_window(rng, 4, 3, 6)), ("composite + landmarks", composite_gen.make_window(rng, 5, 2, 8, F=30)),
+            ("composite mid links", composite_gen.make_window(rng, 4, 5, 6, mid=True))]
+    full = cfg5_marg_gen.make_full((6, 30, 3, 9))
+    out += [("cfg5 full", full), ("cfg5 marginalisation", cfg5_marg_gen.marginalisation_window(full)[0]), ("cfg5 slid, prior > 96 rows", _big_prior_window())]
+    return out
+
+
+VALID = None
+
+
+def valid_windows():
+    global VALID
+    if VALID is None:
+        VALID = _valid_windows()
+    return VALID
+
+
+@pytest.mark.parametrize("n_cu", [256, 8])
+def test_every_window_kind_validates_alone_doubled_and_mixed(n_cu):
+    wins = valid_windows()
+    assert len(wins) >= 14
+    for i, (name, w) in enumerate(wins):
+        rc, msg, info = plan_check([w], n_cu)
+        assert rc == 0, (name, msg)
+        assert info["asm_programs"] == 1
+        rc, msg, info = plan_check([w, w.copy()], n_cu)
+        assert rc == 0, (name, "x2", msg)
+        assert info["asm_programs"] == 1, name            # structurally identical windows share one assembly program
+        mixed = [w, wins[(i + 1) % len(wins)][1], wins[(i + 5) % len(wins)][1]]
+        rc, msg, info = plan_check(mixed, n_cu)
+        assert rc == 0, (name, "mixed", msg)
+    # the tiny chip moves the launch shape with a handful of windows: no fused latency path, one block per window, the auxiliary stream
+    w = wins[0][1]
+    small, big = plan_check([w] * 4, 8)[2], plan_check([w] * 4, 256)[2]            # half a chip of windows: 2 n >= n_cu
+    assert (big["lat_fuse"], big["ls_qpb"], big["ls_folded"]) == (1, 1, 0)
+    assert (small["lat_fuse"], small["ls_qpb"], small["ls_folded"]) == (0, 16, 1)
+    assert plan_check([w] * 5, 8)[2]["want_aux"] == 1 and plan_check([w] * 5, 256)[2]["want_aux"] == 0
+
+
+def test_the_split_prior_is_planned_in_row_chunks():
+    w = _big_prior_window()
+    assert int(w.a["prior_dim"][0]) > 96
+    rc, msg, info = plan_check([w])
+    assert rc == 0, msg
+    nch = (int(w.a["prior_dim"][0]) + 31) // 32
+    assert info["n_pch"] == nch and info["n_pch_split"] == nch
+
+
+@pytest.mark.parametrize("var", [0, 1, 2, 3])
+@pytest.mark.parametrize("qpb", [1, 4, 16])
+def test_forced_schur_classes_and_parts_validate(var, qpb):
+    w = synth.make_window(3, K=4, F=6, S=2, seed=2)
+    for wins in ([w], [w, w.copy(), synth.make_window(3, K=6, F=10, S=3, seed=1)]):
+        rc, msg, info = plan_check(wins, 256, ls_variant=var, ls_qpb=qpb, ls_grad_qpb=qpb)
+        assert rc == 0, msg
+        assert (info["ls_var"], info["ls_qpb"], info["ls_gqpb"]) == (var, qpb, qpb)
+        assert info["ls_folded"] == (1 if qpb == 16 and var <= 1 else 0)
+        rc, msg, _ = plan_check(wins, 8, ls_variant=var, ls_qpb=qpb, flags=3)
+        assert rc == 0, msg
+
+
+def _tiny(**edit):
+    """Two poses + the extrinsic, two landmarks seen from both frames, everything variable in a valid ordering; edit = arrays to replace."""
+    n_pose, n_lm = 3, 2
+    kw = dict(pose=np.tile([0, 0, 0, 0, 0, 0, 1.0], n_pose), sb=np.zeros(0), lm=np.array([0.1, 0.2, 5.0, -0.1, 0.1, 6.0]), sc=np.zeros(0),
+              is_const=np.array([0, 0, 1, 0, 0], np.uint8), order_block=np.array([3, 4, 0, 1], np.int32), order_group=np.array([0, 0, 1, 2], np.int32),
+              proj_idx=np.array([0, 2, 0, 1, 2, 0, 0, 2, 1, 1, 2, 1], np.int32), proj_uv=np.zeros(8))
+    kw.update(edit)
+    from rtk_visual_inertial_navigation_amd.flat import FlatWindow
+    return FlatWindow(**kw)
+
+
+def test_rejections_keep_their_codes_and_messages():
+    assert plan_check([_tiny()])[0] == 0
+    i32 = lambda *v: np.array(v, np.int32)
+    cases = [
+        (_tiny(order_block=i32(3, 4, 0, 7)), E_INVALID, "ordering: block id out of range"),
+        (_tiny(order_block=i32(3, 4, 0, 2)), E_INVALID, "ordering: constant block in ordering"),
+        (_tiny(order_block=i32(3, 4, 0, 0)), E_INVALID, "ordering: block listed twice"),
+        (_tiny(order_group=i32(0, 0, 2, 1)), E_INVALID, "ordering: groups must ascend"),
+        (_tiny(order_block=i32(3, 4, 0), order_group=i32(0, 0, 1)), E_INVALID, "ordering: variable block missing from ordering"),
+        (_tiny(order_block=i32(0, 3, 4, 1), order_group=i32(0, 0, 0, 1)), E_UNSUPPORTED, "pose block in elimination group 0"),
+        (_tiny(proj_idx=i32(0, 2, 0, 1, 2, 0, 0, 2, 1, 1, 2, 2)), E_INVALID, "projection factor: index out of range"),
+    ]
+    for w, code, text in cases:
+        rc, msg, _ = plan_check([w])
+        assert (rc, msg) == (code, text)
+    # a landmark seen from 65 frames: 65 variable poses + the extrinsic, one landmark
+    K = 65
+    w = _tiny(pose=np.tile([0, 0, 0, 0, 0, 0, 1.0], K + 1), lm=np.array([0.1, 0.2, 5.0]), is_const=np.array([0] * K + [1, 0], np.uint8),
+              order_block=i32(K + 1, *range(K)), order_group=i32(0, *range(1, K + 1)),
+              proj_idx=np.array([[k, K, 0] for k in range(K)], np.int32).ravel(), proj_uv=np.zeros(2 * K))
+    assert plan_check([w])[:2] == (E_UNSUPPORTED, "more than 64 observing frames in one window")
+    # ... and from 65 frames of which only two are variable: the frame count passes, the track length does not
+    w = _tiny(pose=np.tile([0, 0, 0, 0, 0, 0, 1.0], K + 1), lm=np.array([0.1, 0.2, 5.0]), is_const=np.array([0, 0] + [1] * (K - 1) + [0], np.uint8),
+              order_block=i32(K + 1, 0, 1), order_group=i32(0, 1, 2),
+              proj_idx=np.array([[k, K, 0] for k in range(K)], np.int32).ravel(), proj_uv=np.zeros(2 * K))
+    assert plan_check([w])[:2] == (E_UNSUPPORTED, "landmark with more than 64 observations")
+    # more than 256 pose blocks (constant ones count: a thread per pose block)
+    K = 257
+    w = _tiny(pose=np.tile([0, 0, 0, 0, 0, 0, 1.0], K), is_const=np.array([0, 0] + [1] * (K - 2) + [0, 0], np.uint8),
+              order_block=i32(K, K + 1, 0, 1), proj_idx=i32(0, 2, 0, 1, 2, 0, 0, 2, 1, 1, 2, 1))
+    assert plan_check([w])[:2] == (E_UNSUPPORTED, "more than 256 pose blocks in a window")
+    # the batch is refused as a whole, and the message is the first offender's
+    assert plan_check([_tiny(), cases[0][0]])[:2] == (E_INVALID, "ordering: block id out of range")
+
+
+def test_the_validator_reports_a_damaged_table():
+    """Negative control: one entry of as_src, sch_rec, s_tnz, prior_colloc, loc2x, a pair_o record and co_voff damaged in the debug
+    entry's private plan."""
+    wins = [synth.make_window(3, K=6, F=10, S=3, seed=1), synth.make_window(3, K=4, F=6, S=2, seed=2)]
+    comp = [composite_gen.make_window(np.random.default_rng(1), 4, 3, 6)]
+    assert plan_check(wins)[0] == 0 and plan_check(comp)[0] == 0
+    for ws, table, index, name in [(wins, 1, 0, "as_src"), (wins, 1, 37, "as_src"), (wins, 2, 0, "sch_rec"), (wins, 2, 8 * 5, "sch_rec"), (wins, 2, 8 * 4 + 2, "sch_rec"),
+                                   (wins, 3, 0, "s_tnz"), (wins, 3, 4, "s_tnz"), (wins, 4, 3, "prior_colloc"), (wins, 5, 0, "loc2x"), (wins, 5, 41, "loc2x"),
+                                   (wins, 7, 2, "pair_o"), (comp, 6, 1, "co_Coff"), (comp, 4, 20, "prior_colloc")]:
+        rc, msg, _ = plan_check(ws, corrupt=(table, index))
+        assert rc == E_INVALID and msg.startswith("plan_validate: " + name), (table, index, msg)
+
+
+def test_plan_runs_clean_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/shim_plan.cpp: the plan of the two ceres-shaped example scenes, built and validated in a stand-alone program compiled
+    from swf_plan.cpp + swf_problem.cpp with -fsanitize=address,undefined (no device code, nothing loaded into Python)."""
+    csrc = os.path.join(ROOT, "rtk_visual_inertial_navigation_amd", "csrc")
+    exe = os.path.join(str(tmp_path), "shim_plan")
+    subprocess.check_call(["g++", "-std=c++17", "-O0", "-g1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "shim_plan.cpp"), os.path.join(csrc, "swf_plan.cpp"), os.path.join(csrc, "swf_problem.cpp"), "-o", exe])
+    # the second scene keeps its hidden epochs in allocations of their own and, like the estimator it imitates, never frees them: the
+    # leak check at exit is off, every other check of both sanitizers is on
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0 and "plans validated: " in r.stdout and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
