@@ -29,6 +29,7 @@
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -644,6 +645,135 @@ inline bool PhaseScreen(const Rover& rover, const double* pose, const double* ba
     }
     out->reset.clear();
     for (int32_t k = 0; k < nr; k++) out->reset.push_back(where[rs[k]]);
+    return true;
+}
+
+// The single-epoch GNSS solve: the seed mini-solve of SWFOptimization::GnssPreprocess (R/swf/swf_gnss.cpp:534-575) and the first fix of
+// GnssProcess (:203-215) for one epoch on the device (swf_gnss_epoch_solve_batch with one epoch; a caller that batches epochs builds
+// the same records and makes one call).  The rows and their weights are those of AddGnssResidual (R/swf/swf_core.cpp:105-203):
+//   USE_RTK    RTKCarrierPhaseFactor per frequency with an RTK_Npoint, el >= el_min (:106-120); clock sys * 2 + f
+//   USE_RTD    RTKPseudorangeFactor per frequency with RTK_P != 0, SVH == 0, RTK_Pstd <= 2, el >= el_min (:122-137); clock sys * 2 + f
+//   then per observation with SVH == 0 and el >= el_min (:140-189), clock 6 + sys * 2:
+//              SppPseudorangeFactor if SPP_P[0] != 0, SPP_Pstd[0] < 2 and no row above was added (have_base); x10 weight when `startup`
+//              SppCarrierPhaseFactor if USE_SPP_PHASE, SPP_L[0] != 0 and an SPP_Npoint[0]
+//              SppCarrierPhaseFactor on SPP_P0[0] if USE_SPP_CORRECTION, SPP_P0[0] != 0 and an SPP_Npoint_PCottections[0]
+//   USE_DOPPLER SppDopplerFactor if SPP_D[0] != 0, SVH == 0, SPP_Dstd[0] <= 2, el >= el_min (:190-203); clock 12
+// The RTK weights are 1 / sqrt(varerr2) with the reference's float sine (R/factor/gnss_factor.cpp:98-103).
+//   rover      the epoch (the reference's mea_t*): obs_count, base_xyz, br_time_diff, obs_data[i].{SVH, sys, el, satellite_pos,
+//              satellite_vel, RTK_L, RTK_Lstd, RTK_P, RTK_Pstd, SPP_P, SPP_Pstd, SPP_L, SPP_Lstd, SPP_P0, SPP_D, SPP_Dstd, ion_var, trop_var,
+//              sat_var, RTK_Npoint, SPP_Npoint, SPP_Npoint_PCottections}, Npoint->{value, continue_count}
+//   pose, speed_bias, gnss_dt   para_pose[g2f[ir]], para_speed_bias[g2f[ir]], para_gnss_dt[0] (13 scalars)
+// Presets: GnssEpochSeed holds pose and speed-bias constant, frees the ambiguities with continue_count <= 10 and runs 2 iterations;
+// GnssEpochFirstFix frees position, velocity, clocks and every ambiguity (the reference sets nothing constant there) and runs 20.
+// The solved values go where ceres::Solve would have left them: pose[0..2], speed_bias[0..2], gnss_dt and the value of every freed
+// ambiguity; a rank-deficient epoch writes nothing back.  The dummy anchor InitialBlackFactor shares no row with the rest
+// and is not part of the operator.
+struct GnssEpochOptions {
+    bool use_rtk = true, use_rtd = true, use_spp_phase = true, use_spp_correction = false, use_doppler = true;
+    bool startup = false;                        // rover_count_accumulate - rover_count + ir < 100 (:154): x10 on the rover-only code weight
+    double el_min = 25.0 * 3.14159265358979323846 / 180.0;      // AZELMIN
+    int nfreq = 2;                               // NFREQ
+    double step_tol = 1e-4, eps_rank = 1e-8;
+};
+enum GnssEpochPreset { GnssEpochSeed = 0, GnssEpochFirstFix = 1 };
+struct GnssEpochRow { int obs, f, kind; bool correction; };           // where a record came from; correction: the SPP_P0 row
+struct GnssEpochResult {
+    std::vector<double> dat;                     // [n][SWF_GES_DOUBLES] as handed over
+    std::vector<int32_t> rec;                    // [n][4]
+    std::vector<GnssEpochRow> rows;              // [n]
+    std::vector<double> N, r;                    // [n]
+    double pos[3], vel[3], clock[SWF_GES_CLOCKS], cost, info[36];
+    int32_t iters, status, clk_rows[SWF_GES_CLOCKS];
+    bool have_base;
+};
+inline double GnssEpochVarerr2(double el, double dt, double mea_var) {
+    const double b = 299792458.0 * 5e-12 * dt, s = (double)sinf((float)el);
+    return mea_var / s / s + b * b;
+}
+template <class Rover, class Lams>
+inline bool GnssEpochSolve(Rover& rover, double* pose, double* speed_bias, double* gnss_dt, const Lams& lams, const GnssEpochOptions& opt,
+                           GnssEpochPreset preset, GnssEpochResult* out) {
+    if (!pose || !speed_bias || !gnss_dt || !out || opt.nfreq < 1 || opt.nfreq > 2 || rover.obs_count < 0) return false;
+    const bool seed = preset == GnssEpochSeed;
+    out->dat.clear(); out->rec.clear(); out->rows.clear();
+    std::vector<double*> amb;                    // where a freed ambiguity lives
+    auto put = [&](int i, int f, int kind, bool corr, const double* sat, const double* sv, double obs, double w, double lam, int slot, double* N,
+                   int continue_count) {
+        const bool fr = N && (!seed || continue_count <= 10);
+        const double row[SWF_GES_DOUBLES] = { sat[0], sat[1], sat[2], sv ? sv[0] : 0.0, sv ? sv[1] : 0.0, sv ? sv[2] : 0.0, obs, w, lam, N ? *N : 0.0 };
+        out->dat.insert(out->dat.end(), row, row + SWF_GES_DOUBLES);
+        const int32_t q[4] = { kind, slot, fr ? SWF_GES_AMB_FREE : 0, 0 };
+        out->rec.insert(out->rec.end(), q, q + 4);
+        out->rows.push_back(GnssEpochRow{ i, f, kind, corr });
+        amb.push_back(fr ? N : nullptr);
+    };
+    const int nobs = rover.obs_count;
+    bool have_base = false;
+    if (opt.use_rtk)
+        for (int i = 0; i < nobs; i++) {
+            auto& d = rover.obs_data[i];
+            for (int f = 0; f < opt.nfreq; f++) {
+                if (!d.RTK_Npoint[f] || d.el < opt.el_min) continue;
+                if (d.sys * 2 + f >= 6) return false;
+                have_base = true;
+                const double lam = lams[d.sys][f], sd = d.RTK_Lstd[f] * lam;
+                put(i, f, SWF_GES_RTK_PHASE, false, d.satellite_pos, nullptr, d.RTK_L[f] * lam, 1.0 / std::sqrt(GnssEpochVarerr2(d.el, rover.br_time_diff, sd * sd)),
+                    lam, d.sys * 2 + f, &d.RTK_Npoint[f]->value, (int)d.RTK_Npoint[f]->continue_count);
+            }
+        }
+    if (opt.use_rtd)
+        for (int i = 0; i < nobs; i++) {
+            auto& d = rover.obs_data[i];
+            for (int f = 0; f < opt.nfreq; f++) {
+                if (d.RTK_P[f] == 0.0 || d.SVH != 0 || d.RTK_Pstd[f] > 2 || d.el < opt.el_min) continue;
+                if (d.sys * 2 + f >= 6) return false;
+                have_base = true;
+                put(i, f, SWF_GES_RTK_CODE, false, d.satellite_pos, nullptr, d.RTK_P[f],
+                    1.0 / std::sqrt(GnssEpochVarerr2(d.el, rover.br_time_diff, d.RTK_Pstd[f] * d.RTK_Pstd[f])), 1.0, d.sys * 2 + f, nullptr, 0);
+            }
+        }
+    for (int i = 0; i < nobs; i++) {
+        auto& d = rover.obs_data[i];
+        if (d.SVH != 0 || d.el < opt.el_min) continue;
+        if (d.sys > 2) return false;
+        const double s = std::sin(d.el), atm = d.ion_var * 0.125 * 0.125 + d.trop_var * 0.7 * 0.7 + d.sat_var * 0.35 * 0.35, lam = lams[d.sys][0];
+        if (d.SPP_P[0] != 0.0 && d.SPP_Pstd[0] < 2 && !have_base) {
+            double istd = s * s / std::sqrt(d.SPP_Pstd[0] * d.SPP_Pstd[0] + (atm + 1));
+            if (opt.startup) istd *= 10;
+            put(i, 0, SWF_GES_SPP_CODE, false, d.satellite_pos, nullptr, d.SPP_P[0], istd, 1.0, 6 + d.sys * 2, nullptr, 0);
+        }
+        if (opt.use_spp_phase && d.SPP_L[0] != 0.0 && d.SPP_Npoint[0]) {
+            const double sd = d.SPP_Lstd[0] * lam;
+            put(i, 0, SWF_GES_SPP_PHASE, false, d.satellite_pos, nullptr, d.SPP_L[0] * lam, s * s / std::sqrt(sd * sd + atm), lam, 6 + d.sys * 2,
+                &d.SPP_Npoint[0]->value, (int)d.SPP_Npoint[0]->continue_count);
+        }
+        if (opt.use_spp_correction && d.SPP_P0[0] != 0.0 && d.SPP_Npoint_PCottections[0])
+            put(i, 0, SWF_GES_SPP_PHASE, true, d.satellite_pos, nullptr, d.SPP_P0[0], s * s / std::sqrt(d.SPP_Pstd[0] * d.SPP_Pstd[0] + atm), lam, 6 + d.sys * 2,
+                &d.SPP_Npoint_PCottections[0]->value, (int)d.SPP_Npoint_PCottections[0]->continue_count);
+    }
+    if (opt.use_doppler)
+        for (int i = 0; i < nobs; i++) {
+            auto& d = rover.obs_data[i];
+            if (d.SPP_D[0] == 0.0 || d.SVH != 0 || d.SPP_Dstd[0] > 2 || d.el < opt.el_min) continue;
+            if (d.sys > 2) return false;
+            const double s = std::sin(d.el), lam = lams[d.sys][0];
+            put(i, 0, SWF_GES_DOPPLER, false, d.satellite_pos, d.satellite_vel, d.SPP_D[0] * lam, s * s / (d.SPP_Dstd[0] * lam), 1.0, 12, nullptr, 0);
+        }
+    out->have_base = have_base;
+    const int32_t n = (int32_t)out->rows.size(), first[2] = { 0, n }, mode = seed ? 0 : (SWF_GES_FREE_POS | SWF_GES_FREE_VEL), cc = 0;
+    out->N.assign((size_t)n + 1, 0.0); out->r.assign((size_t)n + 1, 0.0);
+    std::vector<double> dat = out->dat;
+    std::vector<int32_t> rec = out->rec;
+    dat.resize(dat.size() + SWF_GES_DOUBLES); rec.resize(rec.size() + 4);          // (valid pointers for an epoch without records)
+    if (swf_gnss_epoch_solve_batch(1, first, pose, speed_bias, rover.base_xyz, gnss_dt, &mode, &cc, dat.data(), rec.data(), seed ? 2 : 20,
+                                   opt.step_tol, opt.eps_rank, out->pos, out->vel, out->clock, out->N.data(), out->r.data(), &out->cost,
+                                   &out->iters, &out->status, out->clk_rows, out->info, 0, nullptr) != SWF_OK || out->status < 0) return false;
+    out->N.resize((size_t)n); out->r.resize((size_t)n);
+    if (out->status != SWF_GES_RANK_DEFICIENT) {
+        for (int k = 0; k < 3; k++) { pose[k] = out->pos[k]; speed_bias[k] = out->vel[k]; }
+        for (int k = 0; k < SWF_GES_CLOCKS; k++) gnss_dt[k] = out->clock[k];
+        for (int32_t k = 0; k < n; k++) if (amb[(size_t)k]) *amb[(size_t)k] = out->N[(size_t)k];
+    }
     return true;
 }
 

@@ -64,6 +64,8 @@ enum {
  * swf_problem_fix_prior by parameter-block key.  A linear prior may keep blocks of the parameter_head tail.
  * 110: no layout change; the pre-fit carrier-phase screen on the device: swf_phase_screen_batch (stand-alone: GnssPreprocess's residuals at
  * the predicted pose, their medians per constellation and frequency, the slip flags and the compacted list of ambiguities to re-create).
+ * 111: no layout change; the single-epoch GNSS solve on the device: swf_gnss_epoch_solve_batch (stand-alone: the seed mini-solve of
+ * GnssPreprocess and the first fix of GnssProcess for a batch of epochs, one wavefront each).
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);
@@ -418,8 +420,8 @@ int swf_prior_fix_batch(int32_t n, const int32_t* dim, const double* J, const do
  * inputs cannot be checked by the host: an epoch whose records the kernel finds invalid reports n_reset = -1 and writes nothing else.
  * Any output pointer may be NULL.
  * Stays with the caller: creating the PBtype entries the NEW_AMB flags ask for, continue_count, last_update_time and the 10 s staleness
- * rule (:300-330, :434-495); the pseudorange-correction variables (:474-491); the seed mini-solve (:534-575, a small window the solver
- * already expresses).  For a single epoch the host loop is faster than a launch: the operator is for batched epoch pipelines whose
+ * rule (:300-330, :434-495); the pseudorange-correction variables (:474-491).  The seed mini-solve that follows (:534-575) is
+ * swf_gnss_epoch_solve_batch below.  For a single epoch the host loop is faster than a launch: the operator is for batched epoch pipelines whose
  * inputs and consumers (swf_batch_marginal_priors) are on the device. */
 #define SWF_SCR_NMAX 256           /* MAXOBS (64) x NFREQ (2) x {RTK, SPP} records per epoch */
 enum { SWF_SCR_RTK = 0, SWF_SCR_SPP = 1 };                                   /* kind */
@@ -431,6 +433,68 @@ int swf_phase_screen_batch(int32_t n_epochs, const int32_t* first,
                            const double* dat, const int32_t* rec,
                            double* r, uint8_t* flags, double* med, int32_t* cnt, int32_t* reset, int32_t* n_reset,
                            int32_t on_device, void* stream);
+
+/* Single-epoch GNSS solve: the seed mini-solve of SWFOptimization::GnssPreprocess (R/swf/swf_gnss.cpp:534-575: pose and speed-bias
+ * constant, ambiguities older than ten epochs constant, the receiver clocks and the new ambiguities fitted in two iterations) and the
+ * first fix of GnssProcess (:203-215: one epoch's raw factors, position, velocity and clocks free, 20 iterations) as one operator for
+ * a batch of epochs, one wavefront each.  All five raw GNSS factor classes are scalar rows on the position of the pose, the velocity
+ * of the speed-bias, one of 13 clock scalars and at most one ambiguity (R/factor/gnss_factor.cpp).
+ * Records.  A record is one scalar factor of the epoch.
+ *   dat [n][SWF_GES_DOUBLES]    sat[3] satvel[3] obs w lam N: w = the square-root information the factor would use (1 / sqrt(varerr2) or
+ *                               istd; the operator does not compute varerr2); satvel is read by Doppler rows, lam and N by phase rows
+ *   rec [n][4]                  kind; clock slot 0..12; state bits (SWF_GES_AMB_FREE: the row's ambiguity is an unknown); 0
+ * With xg = pos + base, rho = distance(xg, sat) (the Sagnac term included), clk = clock[slot], sums left to right as written:
+ *   SWF_GES_RTK_PHASE   RTKCarrierPhaseFactor   r = w (rho - N lam - obs + clk)
+ *   SWF_GES_RTK_CODE    RTKPseudorangeFactor    r = w (rho - obs + clk)
+ *   SWF_GES_SPP_CODE    SppPseudorangeFactor    r = w (rho + clk - obs)
+ *   SWF_GES_SPP_PHASE   SppCarrierPhaseFactor (also the pseudorange-correction rows of R/swf/swf_core.cpp:174-186)
+ *                                               r = w (rho + clk - N lam - obs)
+ *   SWF_GES_DOPPLER     SppDopplerFactor        r = w (rate + clk + obs), rate = velecitydistance(): with e = (xg - sat) / |xg - sat| and
+ *                                               ev = vel - satvel, rate = ev . e + OMGE / CLIGHT (satvel[1] xg[0] + sat[1] vel[0] -
+ *                                               satvel[0] xg[1] - sat[0] vel[1])
+ * Jacobians are the factors' own: position w e for range rows (the Sagnac term is not differentiated, as in the reference) and
+ * w (ev - (ev . e) e) / |xg - sat| for Doppler rows; velocity w e for Doppler rows; clock w; ambiguity -w lam.
+ * Inputs per epoch: first [n_epochs + 1] (an epoch without records is legal); pos, vel, base [n_epochs][3]; clock [n_epochs][13];
+ * mode [n_epochs] (SWF_GES_FREE_POS | SWF_GES_FREE_VEL); clk_const [n_epochs]: bit s set = clock s is held constant.
+ * Inputs per call: max_iter, step_tol, eps_rank.
+ * One iteration:
+ *   1. every record is evaluated at the current state.
+ *   2. the reduced system is formed from the rows without AMB_FREE (a free ambiguity is seen by its row alone: its Schur complement is
+ *      zero and the row drops out).  Unknowns: the free part of [pos, vel], and the clocks that are not constant and have at least one
+ *      such row with w > 0.  The normal equations are formed, the clocks eliminated as scalars, and what is left (dimension 0, 3 or 6)
+ *      is factored by Cholesky.
+ *   3. a pivot <= eps_rank x its reduced diagonal entry ends the epoch with SWF_GES_RANK_DEFICIENT, and so does a reduced diagonal
+ *      entry <= eps_rank x that entry before the clocks were eliminated (one that the elimination cancelled to rounding noise).  The
+ *      state outputs of such an epoch are the inputs.
+ *   4. otherwise the clocks are back-substituted and the step is added.
+ *   5. the epoch stops when every entry of the step is <= step_tol in magnitude (SWF_GES_CONVERGED) or after max_iter iterations
+ *      (SWF_GES_MAX_ITER).  A clock without a determining row keeps its value.
+ * After the last iteration every AMB_FREE phase row gets the N that makes its residual zero at the final state: (rho - obs + clk) / lam
+ * (RTK), (rho + clk - obs) / lam (SPP); other rows echo their N.
+ * Outputs, any of which may be NULL: pos_out, vel_out [n_epochs][3]; clock_out [n_epochs][13]; N_out [n]; r_out [n]: the weighted
+ * post-fit residuals, 0 for absorbed rows; cost [n_epochs] = 1/2 sum r^2; iters (iterations run, the deficient one included); status;
+ * clk_rows [n_epochs][13]: the rows without AMB_FREE and with w > 0 per clock; info [n_epochs][36]: the reduced 6 x 6 information matrix
+ * of [pos, vel] at the last linearisation, row-major, with zero rows and columns for the constant part.
+ * An epoch's result does not depend on the other epochs of the call; every sum runs in a fixed order; there are no atomics.
+ * Rejected (host memory: before the device is touched): first[0] != 0 or a decreasing first, a kind, slot, state, mode or clk_const bit
+ * out of range, a non-zero fourth record integer, AMB_FREE on a row that is not a phase row, a non-finite value (records, pos, vel, base,
+ * clock, step_tol, eps_rank), w < 0, lam <= 0 on a phase row, max_iter < 1, null input pointers: SWF_E_INVALID; an epoch with more
+ * than SWF_GES_NMAX records: SWF_E_UNSUPPORTED.  on_device as for swf_lambda_batch; device-resident inputs cannot be checked by the
+ * host: the kernel makes the same checks and an epoch it finds invalid reports status = -1 and writes nothing else.
+ * Stays with the caller: creating the PBtype entries and continue_count (which rows carry AMB_FREE), update_azel (elevation enters
+ * through w), gating on the post-fit residuals, and the dummy anchor InitialBlackFactor, which shares no row with the rest. */
+#define SWF_GES_NMAX 512           /* MAXOBS (64) x 8 rows per satellite */
+enum { SWF_GES_RTK_PHASE = 0, SWF_GES_RTK_CODE = 1, SWF_GES_SPP_CODE = 2, SWF_GES_SPP_PHASE = 3, SWF_GES_DOPPLER = 4 };  /* kind */
+enum { SWF_GES_AMB_FREE = 1 };                                                /* record state bits */
+enum { SWF_GES_FREE_POS = 1, SWF_GES_FREE_VEL = 2 };                          /* epoch mode bits */
+enum { SWF_GES_CONVERGED = 0, SWF_GES_MAX_ITER = 1, SWF_GES_RANK_DEFICIENT = 2 };  /* status (-1: an invalid device-resident epoch) */
+int swf_gnss_epoch_solve_batch(int32_t n_epochs, const int32_t* first,
+                               const double* pos, const double* vel, const double* base, const double* clock,
+                               const int32_t* mode, const int32_t* clk_const, const double* dat, const int32_t* rec,
+                               int32_t max_iter, double step_tol, double eps_rank,
+                               double* pos_out, double* vel_out, double* clock_out, double* N_out, double* r_out, double* cost,
+                               int32_t* iters, int32_t* status, int32_t* clk_rows, double* info,
+                               int32_t on_device, void* stream);
 
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).

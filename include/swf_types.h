@@ -60,6 +60,10 @@ enum { SWF_FIX_DOUBLES = 2 };
 enum { SWF_SCR_DOUBLES = 9 };
 /* (constellation, frequency) groups of the phase screen: sys * 2 + f, as the reference indexes median_error_*[6] (R/swf/swf_gnss.cpp:339) */
 enum { SWF_SCR_GROUPS = 6 };
+/* single-epoch GNSS solve record doubles (swf_gnss_epoch_solve_batch): sat[3] satvel[3] obs w lam N */
+enum { SWF_GES_DOUBLES = 10 };
+/* receiver clock scalars of an epoch, para_gnss_dt[0][0..12]: 0..5 RTK sys * 2 + f, 6..11 rover-only 6 + sys * 2 (+ f), 12 the clock drift */
+enum { SWF_GES_CLOCKS = 13 };
 
 typedef struct swf_flat_window {
     /* ---- parameter pools: caller-owned; read at solve start, written back at solve end */

@@ -60,6 +60,7 @@ EXPORTED = [
     "swf_problem_check_features", "swf_problem_get_feature_check", "swf_problem_rejected_features",
     "swf_prior_fix_batch", "swf_batch_fix_prior", "swf_batch_get_fixed_prior", "swf_batch_install_fixed_prior", "swf_problem_fix_prior",
     "swf_phase_screen_batch",
+    "swf_gnss_epoch_solve_batch",
 ]
 
 
@@ -928,6 +929,104 @@ def phase_screen_batch(first, pos, base, mode, dat, rec, el_min=AZELMIN):
                                       out["n_reset"].ctypes.data_as(pi), C.c_int32(0), None), "swf_phase_screen_batch")
     out["r"], out["flags"], out["reset"] = out["r"][:n], out["flags"][:n], out["reset"][:n]
     out["med"], out["cnt"], out["n_reset"] = out["med"][:E], out["cnt"][:E], out["n_reset"][:E]
+    return out
+
+
+GES_DOUBLES, GES_CLOCKS, GES_NMAX = 10, 13, 512
+GES_RTK_PHASE, GES_RTK_CODE, GES_SPP_CODE, GES_SPP_PHASE, GES_DOPPLER = 0, 1, 2, 3, 4
+GES_AMB_FREE = 1
+GES_FREE_POS, GES_FREE_VEL = 1, 2
+GES_CONVERGED, GES_MAX_ITER, GES_RANK_DEFICIENT = 0, 1, 2
+_CLIGHT = 299792458.0
+
+
+def _ges_istd(el, dt, mea_var):
+    """1 / sqrt(varerr2) of gnss_factor.cpp:98-103: the reference's float sine, correctly rounded (as tests/np_factors.py has it)"""
+    s = np.sin(np.asarray(el, np.float64).astype(np.float32).astype(np.float64)).astype(np.float32).astype(np.float64)
+    b = _CLIGHT * 5e-12 * np.asarray(dt, np.float64)
+    return 1.0 / np.sqrt(np.asarray(mea_var, np.float64) / s / s + b * b)
+
+
+def gnss_epoch_records(cp=None, pr=None, spr=None, scp=None, dop=None):
+    """The unified records of swf_gnss_epoch_solve_batch from the factor records of the flat window, in the order cp, pr, spr, scp, dop:
+      cp  = (dat [k][SWF_CP_DOUBLES = 9], clock slot [k], N [k], free [k])   RTKCarrierPhaseFactor; w = 1 / sqrt(varerr2) or 1 (use_istd = 0)
+      pr  = (dat [k][SWF_PR_DOUBLES = 7], clock slot [k])                    RTKPseudorangeFactor;  w = 1 / sqrt(varerr2)
+      spr = (dat [k][SWF_SPR_DOUBLES = 5], clock slot [k])                   SppPseudorangeFactor;  w = istd
+      scp = (dat [k][SWF_SCP_DOUBLES = 6], clock slot [k], N [k], free [k])  SppCarrierPhaseFactor; w = istd
+      dop = (dat [k][SWF_DOP_DOUBLES = 8], clock slot [k] or None = 12)      SppDopplerFactor;      w = istd
+    Returns (dat [n][10] = sat[3] satvel[3] obs w lam N, rec [n][4] = kind, clock slot, state bits, 0)."""
+    dats, recs = [], []
+
+    def put(kind, d, width, slot, obs, w, lam=None, N=None, free=None, satvel=None):
+        d = np.asarray(d, np.float64).reshape(-1, width)
+        k = d.shape[0]
+        o = np.zeros((k, GES_DOUBLES))
+        o[:, 0:3] = d[:, 0:3]
+        if satvel is not None:
+            o[:, 3:6] = d[:, satvel:satvel + 3]
+        o[:, 6] = d[:, obs]
+        o[:, 7] = w(d)
+        o[:, 8] = d[:, lam] if lam is not None else 1.0
+        o[:, 9] = np.asarray(N, np.float64).reshape(k) if N is not None else 0.0
+        q = np.zeros((k, 4), np.int32)
+        q[:, 0] = kind
+        q[:, 1] = np.asarray(slot, np.int32).reshape(k)
+        if free is not None:
+            q[:, 2] = np.where(np.asarray(free).reshape(k) != 0, GES_AMB_FREE, 0)
+        dats.append(o); recs.append(q)
+
+    if cp is not None:
+        put(GES_RTK_PHASE, cp[0], 9, cp[1], 3, lambda d: np.where(d[:, 8] != 0.0, _ges_istd(d[:, 5], d[:, 6], d[:, 7]), 1.0), lam=4, N=cp[2], free=cp[3])
+    if pr is not None:
+        put(GES_RTK_CODE, pr[0], 7, pr[1], 3, lambda d: _ges_istd(d[:, 4], d[:, 5], d[:, 6]))
+    if spr is not None:
+        put(GES_SPP_CODE, spr[0], 5, spr[1], 3, lambda d: d[:, 4])
+    if scp is not None:
+        put(GES_SPP_PHASE, scp[0], 6, scp[1], 3, lambda d: d[:, 4], lam=5, N=scp[2], free=scp[3])
+    if dop is not None:
+        k = np.asarray(dop[0], np.float64).reshape(-1, 8).shape[0]
+        slot = np.full(k, 12, np.int32) if len(dop) < 2 or dop[1] is None else dop[1]
+        put(GES_DOPPLER, dop[0], 8, slot, 6, lambda d: d[:, 7], satvel=3)
+    if not dats:
+        return np.zeros((0, GES_DOUBLES)), np.zeros((0, 4), np.int32)
+    return np.ascontiguousarray(np.concatenate(dats)), np.ascontiguousarray(np.concatenate(recs))
+
+
+def gnss_epoch_solve_batch(first, pos, vel, base, clock, mode, clk_const, dat, rec, max_iter=20, step_tol=1e-4, eps_rank=1e-8):
+    """The single-epoch GNSS solve for a batch of epochs on the device (swf_gnss_epoch_solve_batch, which see): the seed mini-solve of
+    GnssPreprocess (mode = 0, max_iter = 2) and the first fix of GnssProcess (mode = GES_FREE_POS | GES_FREE_VEL, max_iter = 20).
+    first [E + 1], pos / vel / base [E][3], clock [E][13], mode [E], clk_const [E] (bit s: clock s constant), dat [n][10] = sat[3]
+    satvel[3] obs w lam N, rec [n][4] = kind, clock slot, state bits, 0 (gnss_epoch_records builds both).  Returns dict(pos, vel [E][3],
+    clock [E][13], N [n], r [n], cost [E], iters [E], status [E], clk_rows [E][13], info [E][6][6])."""
+    first = np.ascontiguousarray(first, np.int32).ravel()
+    E = first.size - 1
+    if E < 0:
+        raise ValueError("gnss_epoch_solve_batch: first needs n_epochs + 1 entries")
+    pos, vel, base, clock = (np.ascontiguousarray(v, np.float64).reshape(-1) for v in (pos, vel, base, clock))
+    mode, clk_const = (np.ascontiguousarray(v, np.int32).ravel() for v in (mode, clk_const))
+    dat = np.ascontiguousarray(dat, np.float64).reshape(-1)
+    rec = np.ascontiguousarray(rec, np.int32).reshape(-1)
+    n = dat.size // GES_DOUBLES
+    if (pos.size != 3 * E or vel.size != 3 * E or base.size != 3 * E or clock.size != GES_CLOCKS * E or mode.size != E or clk_const.size != E
+            or dat.size != n * GES_DOUBLES or rec.size != 4 * n or (E and int(first[-1]) > n)):
+        raise ValueError("gnss_epoch_solve_batch: array sizes do not match first")
+    pad = lambda a, k, t: a if a.size else np.zeros(k, t)              # (a valid pointer for an empty array)
+    pos, vel, base, clock = pad(pos, 3, np.float64), pad(vel, 3, np.float64), pad(base, 3, np.float64), pad(clock, GES_CLOCKS, np.float64)
+    mode, clk_const, dat, rec = pad(mode, 1, np.int32), pad(clk_const, 1, np.int32), pad(dat, GES_DOUBLES, np.float64), pad(rec, 4, np.int32)
+    E1, n1 = max(E, 1), max(n, 1)
+    out = dict(pos=np.zeros((E1, 3)), vel=np.zeros((E1, 3)), clock=np.zeros((E1, GES_CLOCKS)), N=np.zeros(n1), r=np.zeros(n1), cost=np.zeros(E1),
+               iters=np.zeros(E1, np.int32), status=np.zeros(E1, np.int32), clk_rows=np.zeros((E1, GES_CLOCKS), np.int32), info=np.zeros((E1, 6, 6)))
+    pi = C.POINTER(C.c_int32)
+    ptr = lambda a: a.ctypes.data_as(_pd if a.dtype == np.float64 else pi)
+    _chk(lib().swf_gnss_epoch_solve_batch(C.c_int32(E), ptr(first), ptr(pos), ptr(vel), ptr(base), ptr(clock), ptr(mode), ptr(clk_const), ptr(dat),
+                                          ptr(rec), C.c_int32(max_iter), C.c_double(step_tol), C.c_double(eps_rank), ptr(out["pos"]),
+                                          ptr(out["vel"]), ptr(out["clock"]), ptr(out["N"]), ptr(out["r"]), ptr(out["cost"]), ptr(out["iters"]),
+                                          ptr(out["status"]), ptr(out["clk_rows"]), ptr(out["info"]), C.c_int32(0), None),
+         "swf_gnss_epoch_solve_batch")
+    for k in ("N", "r"):
+        out[k] = out[k][:n]
+    for k in ("pos", "vel", "clock", "cost", "iters", "status", "clk_rows", "info"):
+        out[k] = out[k][:E]
     return out
 
 
