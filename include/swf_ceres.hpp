@@ -648,6 +648,55 @@ inline bool PhaseScreen(const Rover& rover, const double* pose, const double* ba
     return true;
 }
 
+// The double-difference pairs of the ambiguity search: FindReferenceSatellites and the loop of SWFOptimization::LambdaSearch that builds
+// D3 (R/swf/swf_lambda.cpp:8-53, 118-188) for one window on the device (swf_dd_select_batch with one window; a caller that batches
+// windows builds the same records and makes one call, or stays on the device with swf_batch_select_ambiguity_pairs).
+//   rovers     the window's epochs, oldest first as the reference keeps them (rovers[0 .. rover_count-1], each a mea_t*): obs_count,
+//              obs_data[i].{sys, RTK_Npoint}, Npoint->value; read only.  The epochs are handed over newest first (:126).
+//   tail_of    tail_of(&Npoint->value) = the ambiguity's coordinate in the parameter_head tail, parameter_block_idx[...] - m of the
+//              reference's MarginalizationInfo (:17, :151), or a negative number when the block is absent or not in the tail: such an
+//              observation is left out, as it can produce neither a candidate nor a pair.  n = the tail dimension.
+//   gate       last_fix ? 0.2 : 1.4 (:163)
+// On success out->pairs holds the rows of D in the reference's order, (a, b) = +1 at a, -1 at b; out->go() is false where the
+// reference returns early (:96, :178, :184).  The `use` marks, the fix counter and last_fix stay with the caller.
+struct DoubleDifferenceSelection {
+    std::vector<std::pair<int, int> > pairs;
+    int last_count = 0, last_ref_count = 0, info = -1;       // info: SWF_DDSEL_*
+    bool go() const { return info == SWF_DDSEL_OK; }
+};
+template <class Rovers, class TailOf>
+inline bool SelectDoubleDifferences(const Rovers& rovers, int rover_count, TailOf tail_of, int n, double gate,
+                                    DoubleDifferenceSelection* out, int nfreq = 2) {
+    if (!out || rover_count < 0 || n < 0 || nfreq < 1 || nfreq > 2) return false;
+    std::vector<int32_t> obs_first(1, 0), obs;
+    std::vector<double> y((size_t)n + 1, 0.0);
+    for (int ir = rover_count - 1; ir >= 0; ir--) {
+        const auto& rover = *rovers[ir];
+        for (int i = 0; i < rover.obs_count; i++) {
+            const auto& d = rover.obs_data[i];
+            for (int f = 0; f < nfreq; f++) {
+                const auto* np_ = d.RTK_Npoint[f];
+                if (!np_) continue;
+                const int a = (int)tail_of(&np_->value);
+                if (a < 0 || a >= n) continue;
+                if (d.sys < 0 || d.sys * 2 + f >= 6) return false;
+                obs.push_back(d.sys * 2 + f); obs.push_back(a);
+                y[(size_t)a] = np_->value;
+            }
+        }
+        obs_first.push_back((int32_t)(obs.size() / 2));
+    }
+    const int32_t epoch_first[2] = { 0, (int32_t)rover_count }, y_first[2] = { 0, (int32_t)n };
+    int32_t pairs[SWF_LAMBDA_NMAX * 2], counts[4] = { 0, 0, 0, -1 };
+    obs.resize(obs.size() + 2);                              // (a valid pointer for a window without observations)
+    if (swf_dd_select_batch(1, epoch_first, obs_first.data(), obs.data(), y_first, y.data(), &gate, pairs, counts, nullptr, nullptr, nullptr,
+                            0, nullptr) != SWF_OK) return false;
+    out->pairs.clear();
+    for (int i = 0; i < counts[0]; i++) out->pairs.push_back(std::make_pair((int)pairs[2 * i], (int)pairs[2 * i + 1]));
+    out->last_count = counts[1]; out->last_ref_count = counts[2]; out->info = counts[3];
+    return true;
+}
+
 // The single-epoch GNSS solve: the seed mini-solve of SWFOptimization::GnssPreprocess (R/swf/swf_gnss.cpp:534-575) and the first fix of
 // GnssProcess (:203-215) for one epoch on the device (swf_gnss_epoch_solve_batch with one epoch; a caller that batches epochs builds
 // the same records and makes one call).  The rows and their weights are those of AddGnssResidual (R/swf/swf_core.cpp:105-203):

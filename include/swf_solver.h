@@ -66,6 +66,10 @@ enum {
  * the predicted pose, their medians per constellation and frequency, the slip flags and the compacted list of ambiguities to re-create).
  * 111: no layout change; the single-epoch GNSS solve on the device: swf_gnss_epoch_solve_batch (stand-alone: the seed mini-solve of
  * GnssPreprocess and the first fix of GnssProcess for a batch of epochs, one wavefront each).
+ * 112: no layout change; the double-difference pairs of the ambiguity search chosen on the device: swf_dd_select_batch (stand-alone:
+ * FindReferenceSatellites and LambdaSearch's D3 loop for a batch of windows, one wavefront each), swf_batch_select_ambiguity_pairs /
+ * swf_batch_ambiguity_search_selected / swf_batch_get_ambiguity_pairs (solve, tail covariance, pair selection, LAMBDA and ratio test as
+ * one enqueue).  swf_batch_ambiguity_search with host pairs is unchanged.
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);
@@ -216,12 +220,33 @@ int swf_batch_get_tail_covariance(swf_batch* b, int32_t w, double* A, double* Qy
  * read that copy.  Every pointer may be NULL.  F [2][n_b] (candidate j at F[j * n_b + i]), s [2], ratio [2], fixed [1],
  * Qb [n_b][n_b] row-major and bf [n_b] (the search's own inputs, so that a caller can replay them), n_b, info (SWF_LAMBDA_*).
  * ratio / fixed are 0 unless info == SWF_LAMBDA_OK.  The search results are invalidated by the next swf_batch_solve
- * (SWF_E_STATE).  Stays with the caller: the choice of the reference satellites and the fractional-part gating of D's rows (:163),
- * the early returns on too few rows (:178, :184) and the fix counter.  The new prior of FixedIntegerFactors (:250-355) is
- * swf_batch_fix_prior below. */
+ * (SWF_E_STATE).  Stays with the caller of THIS entry point: the choice of the reference satellites and the fractional-part gating of
+ * D's rows (:163), the early returns on too few rows (:178, :184) — swf_batch_select_ambiguity_pairs below makes them on the device —
+ * and the fix counter.  The new prior of FixedIntegerFactors (:250-355) is swf_batch_fix_prior below. */
 int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_first, const int32_t* pairs, double ratio_threshold);
 int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, double* s, double* ratio, int32_t* fixed,
                                 double* Qb, double* bf, int32_t* n_b, int32_t* info);
+
+/* The pairs of the search chosen on the device (the operator of swf_dd_select_batch, which see, on the batch's own state): with it
+ * solve -> tail covariance -> pair selection -> LAMBDA -> ratio test is one uninterrupted enqueue.
+ * swf_batch_select_ambiguity_pairs needs a solve (SWF_E_STATE otherwise) and is asynchronous on the batch stream; epoch_first, obs_first,
+ * obs and gate are host arrays as for swf_dd_select_batch, t being a coordinate of the window's parameter_head tail, and y the device
+ * state at that moment, as in the search.  Refused with SWF_E_INVALID before anything is enqueued: what swf_dd_select_batch refuses, and
+ * a t on a tail block whose size is not 1; more than SWF_DDSEL_NMAX observations in an epoch or a tail beyond SWF_DDSEL_TMAX:
+ * SWF_E_UNSUPPORTED.  The pairs go into window w's 64-slot range of the search's own device pair table, with a device pair count that is
+ * 0 unless the window's info == SWF_DDSEL_OK (the reference's early returns).  A selection replaces the pair table: results of an
+ * earlier search or fix_prior are invalidated (SWF_E_STATE from their getters).
+ * swf_batch_ambiguity_search_selected needs a selection after the last solve and a tail covariance (SWF_E_STATE otherwise) and runs the
+ * search of swf_batch_ambiguity_search on the selected pairs: every field swf_batch_get_ambiguity_fix returns equals, bit for bit, what
+ * swf_batch_ambiguity_search returns for the same pairs passed from the host.  A window whose count is 0 reports SWF_LAMBDA_NO_INPUT.
+ * swf_batch_get_ambiguity_pairs synchronises; its first call after a selection copies every window's selection in one transfer per
+ * array.  pairs [64][2], counts [4], refs [epochs of w][6], cost / role [observations of w], as swf_dd_select_batch; any may be NULL.
+ * swf_batch_fix_prior after a selected search reads the selection back in the same way (n_use: the reference takes counts[1] =
+ * last_count).  The reference's host reads `fixed` for its fix counter at that point anyway: this is the one synchronisation of the chain.
+ * A new solve, a state upload, a state reset or a swf_batch_ambiguity_search with host pairs invalidates the selection (SWF_E_STATE). */
+int swf_batch_select_ambiguity_pairs(swf_batch* b, const int32_t* epoch_first, const int32_t* obs_first, const int32_t* obs, const double* gate);
+int swf_batch_ambiguity_search_selected(swf_batch* b, double ratio_threshold);
+int swf_batch_get_ambiguity_pairs(swf_batch* b, int32_t w, int32_t* pairs, int32_t* counts, int32_t* refs, double* cost, uint8_t* role);
 
 /* Fix and hold: the second half of SWFOptimization::LambdaSearch (R/swf/swf_lambda.cpp:249-355) for every window, on the device.  The
  * reference builds a MarginalizationInfo from the window prior, adds FixedIntegerFactor(ROUND(F), 1/0.03) per double difference and
@@ -495,6 +520,56 @@ int swf_gnss_epoch_solve_batch(int32_t n_epochs, const int32_t* first,
                                double* pos_out, double* vel_out, double* clock_out, double* N_out, double* r_out, double* cost,
                                int32_t* iters, int32_t* status, int32_t* clk_rows, double* info,
                                int32_t on_device, void* stream);
+
+/* The double-difference pairs of the integer ambiguity search: FindReferenceSatellites (R/swf/swf_lambda.cpp:8-53) and the loop of
+ * SWFOptimization::LambdaSearch that builds D3 (:118-188) for a batch of windows, one wavefront each.
+ *   epoch_first [n_windows + 1]   window w owns epochs epoch_first[w] .. epoch_first[w+1]-1, in the reference's processing order:
+ *                                 NEWEST FIRST (ir = rover_count-1 .. 0); a window without epochs is legal
+ *   obs_first [n_epochs + 1]      epoch e owns observations obs_first[e] .. obs_first[e+1]-1, in the reference's iteration order
+ *                                 (observation index ascending, frequency ascending); an epoch without observations is legal
+ *   obs [n_obs][2]                class = sys * 2 + f in 0..5; t = the tail coordinate of the observation's ambiguity
+ *   y_first [n_windows + 1], y    window w's tail has y_first[w+1] - y_first[w] coordinates, y[y_first[w] + t] the float value of t
+ *   gate [n_windows]              the reference: 0.2 after a fix, 1.4 otherwise (:163)
+ * Observations whose ambiguity is absent or not in the tail are left out by the caller: they can never be candidates (:14-18) nor
+ * produce a pair (:150-154), their `use` marks are only ever read for themselves, and the :141-144 fallback that names one as a
+ * reference can only lead to the a < 0 || b < 0 exit.  The reference reads a block at index 0 of parameter_block_idx as absent
+ * (:16, :150); which observations are passed is the caller's decision.
+ * Per window (round = C round(), halves away from zero; every sum left to right; no product anywhere):
+ *   used = {}; for each epoch, newest first:
+ *     for each class c: the candidates are the epoch's observations of class c with t not in used, in order; without one the class
+ *       has no reference in this epoch; cost_j = sum over the candidates i of |s - round(s)|, s = y[t_i] - y[t_j] (i == j included);
+ *       the reference is the LAST candidate whose cost equals the minimum.  A reference is never marked used.
+ *     for each observation k in order: its class has no reference: role 4.  Else t_k in used: role 0.  Else k is the reference:
+ *       role 1.  Else t_k is marked used (before the gate: a gated-out ambiguity is not reconsidered in an older epoch) and, with
+ *       d = y[t_k] - y[t_ref], |d - round(d)| < gate appends the pair (t_k, t_ref): role 2; otherwise role 3.
+ *   last_count = the pairs of the newest epoch, last_ref_count = its classes with a reference;
+ *   go = tail >= 6 && last_count + last_ref_count >= 6 && last_count >= 4 && n_pairs >= 4  (:96, :178, :184).
+ * Outputs, any of which may be NULL: pairs [n_windows][64][2] in the order they were appended, -1 behind them; counts [n_windows][4]
+ * = n_pairs, last_count, last_ref_count, info; refs [n_epochs][6] = the reference's observation index within the epoch, or -1;
+ * cost [n_obs], -1 where the observation was no candidate; role [n_obs] (SWF_DDSEL_SKIPPED ..).
+ *   info  SWF_DDSEL_OK         go
+ *         SWF_DDSEL_TOO_FEW    the reference's early returns; pairs and counts are still reported
+ *         SWF_DDSEL_OVERFLOW   more than SWF_LAMBDA_NMAX pairs: n_pairs = 0 and no pair is reported; the other outputs are
+ *         SWF_DDSEL_NONFINITE  some y the window's observations name is not finite (every ambiguity is a candidate where it first
+ *                              appears, and the reference sorts the costs, which is undefined with a NaN): counts = 0, refs = -1,
+ *                              cost = -1, role = 0, no pair
+ * A window's result does not depend on the other windows of the call and is a function of its inputs alone, bit for bit.
+ * Rejected (host memory: before the device is touched, no output written): first[0] != 0 or a decreasing prefix array, a class outside
+ * 0..5, a t outside the tail, one t twice within an epoch, a gate that is not finite and positive, null input pointers: SWF_E_INVALID;
+ * an epoch with more than SWF_DDSEL_NMAX observations or a tail of more than SWF_DDSEL_TMAX coordinates: SWF_E_UNSUPPORTED.
+ * on_device as for swf_preintegrate_batch: every pointer is device memory, the call is asynchronous on `stream`, and the kernel makes
+ * the checks itself (one t twice within an epoch excepted): a window it finds invalid reports info = -1 and writes nothing else.
+ * Stays with the caller: the fix counter, the gnss_last_updatetime reset, and which ambiguities are in the tail
+ * (UpdateNParameterHead's eligibility rules).  For a single window the host loop is faster than a launch: the operator is for batches
+ * whose state and whose consumer (swf_batch_ambiguity_search_selected) are on the device. */
+#define SWF_DDSEL_NMAX 256          /* MAXOBS (64) x NFREQ (2), with room: observations per epoch */
+#define SWF_DDSEL_TMAX 2048         /* tail coordinates per window */
+enum { SWF_DDSEL_OK = 0, SWF_DDSEL_TOO_FEW = 1, SWF_DDSEL_OVERFLOW = 2, SWF_DDSEL_NONFINITE = 3 };             /* info */
+enum { SWF_DDSEL_SKIPPED = 0, SWF_DDSEL_REFERENCE = 1, SWF_DDSEL_PAIRED = 2, SWF_DDSEL_GATED_OUT = 3, SWF_DDSEL_NO_REFERENCE = 4 };  /* role */
+int swf_dd_select_batch(int32_t n_windows, const int32_t* epoch_first, const int32_t* obs_first, const int32_t* obs,
+                        const int32_t* y_first, const double* y, const double* gate,
+                        int32_t* pairs, int32_t* counts, int32_t* refs, double* cost, uint8_t* role,
+                        int32_t on_device, void* stream);
 
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).

@@ -19,6 +19,7 @@
 #include "swf_kernels3.h"
 #include "swf_kernels4.h"
 #include "swf_lambda.h"
+#include "swf_ddselect.h"
 #include "swf_features.h"
 #include "swf_fixprior.h"
 #include "swf_plan.h"
@@ -29,7 +30,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 extern "C" const char* swf_last_error(void) { return g_err.c_str(); }
 void swf_internal_set_error(const std::string& m) { g_err = m; }
-extern "C" int swf_version(void) { return 111; }
+extern "C" int swf_version(void) { return 112; }
 extern "C" int swf_abi_sizes(int32_t out[5]) {
     if (!out) return fail(SWF_E_INVALID, "swf_abi_sizes: null");
     out[0] = (int32_t)sizeof(swf_options); out[1] = (int32_t)sizeof(swf_summary); out[2] = (int32_t)sizeof(swf_timing);
@@ -225,6 +226,15 @@ struct swf_batch {
     bool am_valid = false, am_host = false; std::vector<double> h_am;
     std::vector<int> am_nb;                             // pairs per window of the last search
     std::vector<int> am_h_first; std::vector<int4> am_h_pairs;      // host staging of the pair upload (outlives the asynchronous copy)
+    // double-difference pair selection (swf_ddselect.h).  Per-window outputs from the pool at the first selection; the inputs and the
+    // per-epoch / per-observation outputs, whose sizes change from call to call, in two buffers that grow on demand.  dd_h_in stages
+    // the upload (gate | epoch_first | obs_first | obs | state index) and keeps the prefix arrays for the getter.
+    int* dd_pairs = nullptr; int* dd_counts = nullptr; int* dd_npair = nullptr;
+    char* dd_in = nullptr; char* dd_out = nullptr; size_t dd_in_cap = 0, dd_out_cap = 0; int dd_ne = 0, dd_no = 0;
+    std::vector<char> dd_h_in, dd_h_out; std::vector<int> dd_h_pairs, dd_h_counts;
+    bool dd_valid = false, dd_host = false;
+    const int* dd_tail = nullptr;                       // the tail dimensions on the device, when no tail covariance has put them there
+    bool am_selected = false, am_sel_host = false;      // the last search ran on the selection; am_h_pairs / am_h_first / am_nb have been read back
     // fix and hold (swf_fixprior.h; allocated at the first swf_batch_fix_prior for the batch's largest linear prior): per-window table,
     // tail-coordinate -> prior-column table, result slabs of fx_ldn^2 / fx_ldn / fx_ldx doubles per window, mirrored to the host by the first getter
     FixWin* fx_win = nullptr; int* fx_tailcol = nullptr; double* fx_A = nullptr; double* fx_b = nullptr; double* fx_J = nullptr; double* fx_r0 = nullptr;
@@ -471,6 +481,8 @@ extern "C" int swf_batch_destroy(swf_batch* b) {
     for (auto& e : b->ev) handle_cache().give(e, true);
     if (b->h_x) (void)hipHostFree(b->h_x);
     if (b->h_sum) (void)hipHostFree(b->h_sum);
+    if (b->dd_in) (void)hipFree(b->dd_in);
+    if (b->dd_out) (void)hipFree(b->dd_out);
     b->pool.release();
     delete b;
     return SWF_OK;
@@ -511,14 +523,14 @@ extern "C" int swf_batch_upload_state(swf_batch* b) {
         HIPCHK(hipMemsetAsync(b->CA.history, 0, (size_t)b->n_comp * sizeof(int), b->stream));
     }
     HIPCHK(hipStreamSynchronize(b->stream));     // staging buffers have stack lifetime
-    b->fc_valid = false;
+    b->fc_valid = false; b->dd_valid = false;
     return SWF_OK;
 }
 
 extern "C" int swf_batch_reset_state(swf_batch* b) {
     DeviceGuard dg_(b ? b->device : -1);
     if (!b) return fail(SWF_E_INVALID, "null batch");
-    b->fc_valid = false;
+    b->fc_valid = false; b->dd_valid = false;
     int n = b->D.n_x;
     hipLaunchKernelGGL(k_copy, dim3((n + 255) / 256), dim3(256), 0, b->stream, b->D.x, (const double*)b->D.x0, n);
     HIPCHK(hipGetLastError());
@@ -940,7 +952,7 @@ extern "C" int swf_batch_solve(swf_batch* b, const swf_options* opt) {
     b->last.lm_schur_flops = b->lm_schur_flops; b->last.n_obs = b->D.n_proj;
     b->last.lm_schur_flops_sym = b->lm_schur_flops_sym; b->last.lm_schur_mfma = b->lm_schur_mfma;
     b->last.n_linearizations = nlin;
-    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false; b->am_valid = false; b->fx_valid = false; b->fc_valid = false;      // consumer outputs belong to the previous solve
+    b->last_mode = opt->step_mode; b->mg_valid = false; b->tc_valid = false; b->am_valid = false; b->fx_valid = false; b->fc_valid = false; b->dd_valid = false;      // consumer outputs belong to the previous solve
     return SWF_OK;
 }
 
@@ -1235,6 +1247,17 @@ extern "C" int swf_batch_get_tail_covariance(swf_batch* b, int32_t w, double* A,
     return SWF_OK;
 }
 
+// the search's device buffers, sized for the most a search may pass (n_windows x 64 pairs)
+static int am_alloc(swf_batch* b) {
+    if (b->am_rec) return 0;
+    const size_t nw = b->win.size();
+    int rc = 0;
+    rc |= b->pool.zeros(nw + 1, &b->am_first);
+    rc |= b->pool.zeros(nw * SWF_LAMBDA_NMAX, &b->am_pairs);
+    rc |= b->pool.zeros(nw * (LBD_REC_QB + SWF_LAMBDA_NMAX * SWF_LAMBDA_NMAX), &b->am_rec);
+    return rc;
+}
+
 // integer ambiguity search (LambdaSearch's numeric core): gather D Qy D^T and D y, LAMBDA with m = 2, ratio test — one k_lambda<true>
 extern "C" int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_first, const int32_t* pairs, double ratio_threshold) {
     DeviceGuard dg_(b ? b->device : -1);
@@ -1265,13 +1288,8 @@ extern "C" int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_firs
             pr[q] = make_int4(ta, tb, xa, xb);
         }
     }
-    if (!b->am_rec) {
-        int rc = 0;
-        rc |= b->pool.zeros((size_t)nw + 1, &b->am_first);
-        rc |= b->pool.zeros((size_t)nw * SWF_LAMBDA_NMAX, &b->am_pairs);
-        rc |= b->pool.zeros((size_t)nw * (LBD_REC_QB + SWF_LAMBDA_NMAX * SWF_LAMBDA_NMAX), &b->am_rec);
-        if (rc) return fail(SWF_E_NODEVICE, "device allocation failed");
-    }
+    if (am_alloc(b)) return fail(SWF_E_NODEVICE, "device allocation failed");
+    b->dd_valid = false;                         // the pair table is this search's from here on
     b->am_h_first.assign(pair_first, pair_first + nw + 1);
     HIPCHK(hipMemcpyAsync(b->am_first, b->am_h_first.data(), (size_t)(nw + 1) * sizeof(int), hipMemcpyHostToDevice, b->stream));
     if (total > 0) HIPCHK(hipMemcpyAsync(b->am_pairs, pr.data(), (size_t)total * sizeof(int4), hipMemcpyHostToDevice, b->stream));
@@ -1284,7 +1302,160 @@ extern "C" int swf_batch_ambiguity_search(swf_batch* b, const int32_t* pair_firs
     const int rc = swf_internal_lambda_launch(A, true, b->stream);
     if (rc) return rc;
     b->am_nb = nb; b->am_rec_ld = A.rec_ld;
-    b->am_valid = true; b->am_host = false;
+    b->am_valid = true; b->am_host = false; b->am_selected = false;
+    return SWF_OK;
+}
+
+// ---- the pairs chosen on the device (k_dd_select<true>) and the search on them (k_lambda<true, true>)
+static size_t dd_up8(size_t n) { return (n + 7) & ~(size_t)7; }
+struct DdLayout {           // byte offsets in dd_in / dd_out for nw windows, ne epochs, no observations
+    size_t gate, efirst, ofirst, obs, xidx, in_bytes, cost, refs, role, out_bytes;
+    DdLayout(size_t nw, size_t ne, size_t no) {
+        gate = 0; efirst = gate + nw * sizeof(double); ofirst = dd_up8(efirst + (nw + 1) * sizeof(int)); obs = dd_up8(ofirst + (ne + 1) * sizeof(int));
+        xidx = dd_up8(obs + std::max<size_t>(no, 1) * 2 * sizeof(int)); in_bytes = dd_up8(xidx + std::max<size_t>(no, 1) * sizeof(int));
+        cost = 0; refs = std::max<size_t>(no, 1) * sizeof(double); role = dd_up8(refs + std::max<size_t>(ne, 1) * DDS_CLASSES * sizeof(int));
+        out_bytes = dd_up8(role + std::max<size_t>(no, 1));
+    }
+};
+
+extern "C" int swf_batch_select_ambiguity_pairs(swf_batch* b, const int32_t* epoch_first, const int32_t* obs_first, const int32_t* obs, const double* gate) {
+    DeviceGuard dg_(b ? b->device : -1);
+    const char* who = "swf_batch_select_ambiguity_pairs";
+    if (!b || !epoch_first || !obs_first || !gate) return fail(SWF_E_INVALID, std::string(who) + ": null argument");
+    if (b->last_mode < 0) return fail(SWF_E_STATE, std::string(who) + " needs a preceding solve");
+    const int nw = (int)b->win.size();
+    std::vector<int32_t> tail((size_t)nw);
+    for (int w = 0; w < nw; w++) tail[(size_t)w] = b->hw[w].tail_dim;
+    const int chk = swf_internal_dd_select_check(who, nw, epoch_first, obs_first, obs, tail.data(), gate);
+    if (chk) return chk;
+    const int ne = epoch_first[nw], no = obs_first[ne];
+    const DdLayout L((size_t)nw, (size_t)ne, (size_t)no);
+    // validated into a local staging area: a refused call leaves the previous selection as it was
+    std::vector<char> in(L.in_bytes, 0);
+    memcpy(in.data() + L.gate, gate, (size_t)nw * sizeof(double));
+    memcpy(in.data() + L.efirst, epoch_first, (size_t)(nw + 1) * sizeof(int));
+    memcpy(in.data() + L.ofirst, obs_first, (size_t)(ne + 1) * sizeof(int));
+    if (no) memcpy(in.data() + L.obs, obs, (size_t)no * 2 * sizeof(int));
+    int* xi = (int*)(in.data() + L.xidx);
+    for (int w = 0; w < nw; w++) {
+        const HostWin& h = b->hw[w];
+        for (int i = obs_first[epoch_first[w]]; i < obs_first[epoch_first[w + 1]]; i++) {
+            xi[i] = h.tail_x[(size_t)obs[2 * (size_t)i + 1]];
+            if (xi[i] < 0) return fail(SWF_E_INVALID, std::string(who) + ": an observation on a tail block whose size is not 1 (window " + std::to_string(w) + ")");
+        }
+    }
+    if (am_alloc(b)) return fail(SWF_E_NODEVICE, "device allocation failed");
+    if (!b->dd_pairs) {
+        int rc = 0;
+        rc |= b->pool.zeros((size_t)nw * SWF_LAMBDA_NMAX * 2, &b->dd_pairs); rc |= b->pool.zeros((size_t)nw * 4, &b->dd_counts); rc |= b->pool.zeros((size_t)nw, &b->dd_npair);
+        if (rc) return fail(SWF_E_NODEVICE, "device allocation failed");
+    }
+    if (L.in_bytes > b->dd_in_cap || L.out_bytes > b->dd_out_cap) {      // (hipFree waits for the work that still reads the old buffers)
+        if (b->dd_in) (void)hipFree(b->dd_in);
+        if (b->dd_out) (void)hipFree(b->dd_out);
+        b->dd_in = b->dd_out = nullptr; b->dd_in_cap = b->dd_out_cap = 0; b->dd_valid = false;
+        HIPCHK(hipMalloc((void**)&b->dd_in, L.in_bytes * 2));
+        HIPCHK(hipMalloc((void**)&b->dd_out, L.out_bytes * 2));
+        b->dd_in_cap = L.in_bytes * 2; b->dd_out_cap = L.out_bytes * 2;
+    }
+    if (!b->tc_tail && !b->dd_tail) {            // the tail dimensions on the device (swf_batch_tail_covariance keeps its own copy likewise)
+        std::vector<int> td(tail.begin(), tail.end());
+        if (b->pool.put(td, &b->dd_tail)) return fail(SWF_E_NODEVICE, "device allocation failed");
+    }
+    // from here on the pair table and the selection buffers belong to this call
+    b->dd_valid = false; b->am_valid = false; b->fx_valid = false;
+    b->dd_h_in.swap(in); b->dd_ne = ne; b->dd_no = no;
+    HIPCHK(hipMemcpyAsync(b->dd_in, b->dd_h_in.data(), L.in_bytes, hipMemcpyHostToDevice, b->stream));
+    DdSelectArgs A{};
+    A.n_windows = nw;
+    A.gate = (const double*)(b->dd_in + L.gate); A.epoch_first = (const int*)(b->dd_in + L.efirst); A.obs_first = (const int*)(b->dd_in + L.ofirst);
+    A.obs = (const int*)(b->dd_in + L.obs); A.xidx = (const int*)(b->dd_in + L.xidx);
+    A.tail = b->tc_tail ? b->tc_tail : b->dd_tail; A.x = b->D.x;
+    A.pairs = b->dd_pairs; A.counts = b->dd_counts; A.pair_count = b->dd_npair;
+    A.cost = (double*)(b->dd_out + L.cost); A.refs = (int*)(b->dd_out + L.refs); A.role = (unsigned char*)(b->dd_out + L.role);
+    A.am_pairs = b->am_pairs; A.am_first = b->am_first;
+    const int rc = swf_internal_dd_select_launch(A, true, b->stream);
+    if (rc) return rc;
+    b->dd_valid = true; b->dd_host = false;
+    return SWF_OK;
+}
+
+// one transfer per array: the selection of every window on the host
+static int dd_fetch(swf_batch* b) {
+    if (b->dd_host) return SWF_OK;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    const size_t nw = b->win.size();
+    const DdLayout L(nw, (size_t)b->dd_ne, (size_t)b->dd_no);
+    b->dd_h_pairs.resize(nw * SWF_LAMBDA_NMAX * 2); b->dd_h_counts.resize(nw * 4); b->dd_h_out.resize(L.out_bytes);
+    HIPCHK(hipMemcpy(b->dd_h_pairs.data(), b->dd_pairs, b->dd_h_pairs.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(b->dd_h_counts.data(), b->dd_counts, b->dd_h_counts.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (b->dd_ne) HIPCHK(hipMemcpy(b->dd_h_out.data() + L.refs, b->dd_out + L.refs, (size_t)b->dd_ne * DDS_CLASSES * sizeof(int), hipMemcpyDeviceToHost));
+    if (b->dd_no) {
+        HIPCHK(hipMemcpy(b->dd_h_out.data() + L.cost, b->dd_out + L.cost, (size_t)b->dd_no * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(b->dd_h_out.data() + L.role, b->dd_out + L.role, (size_t)b->dd_no, hipMemcpyDeviceToHost));
+    }
+    b->dd_host = true;
+    return SWF_OK;
+}
+
+extern "C" int swf_batch_get_ambiguity_pairs(swf_batch* b, int32_t w, int32_t* pairs, int32_t* counts, int32_t* refs, double* cost, uint8_t* role) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b || w < 0 || w >= (int)b->win.size()) return fail(SWF_E_INVALID, "bad window index");
+    if (!b->dd_valid) return fail(SWF_E_STATE, "swf_batch_get_ambiguity_pairs before swf_batch_select_ambiguity_pairs (or after a new solve, state upload or reset)");
+    const int rc = dd_fetch(b);
+    if (rc) return rc;
+    const size_t nw = b->win.size();
+    const DdLayout L(nw, (size_t)b->dd_ne, (size_t)b->dd_no);
+    const int* ef = (const int*)(b->dd_h_in.data() + L.efirst); const int* of = (const int*)(b->dd_h_in.data() + L.ofirst);
+    const size_t e0 = (size_t)ef[w], e1 = (size_t)ef[w + 1], o0 = (size_t)of[e0], o1 = (size_t)of[e1];
+    if (pairs) memcpy(pairs, b->dd_h_pairs.data() + (size_t)w * SWF_LAMBDA_NMAX * 2, SWF_LAMBDA_NMAX * 2 * sizeof(int));
+    if (counts) memcpy(counts, b->dd_h_counts.data() + (size_t)w * 4, 4 * sizeof(int));
+    if (refs && e1 > e0) memcpy(refs, b->dd_h_out.data() + L.refs + e0 * DDS_CLASSES * sizeof(int), (e1 - e0) * DDS_CLASSES * sizeof(int));
+    if (cost && o1 > o0) memcpy(cost, b->dd_h_out.data() + L.cost + o0 * sizeof(double), (o1 - o0) * sizeof(double));
+    if (role && o1 > o0) memcpy(role, b->dd_h_out.data() + L.role + o0, o1 - o0);
+    return SWF_OK;
+}
+
+extern "C" int swf_batch_ambiguity_search_selected(swf_batch* b, double ratio_threshold) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b) return fail(SWF_E_INVALID, "swf_batch_ambiguity_search_selected: null batch");
+    if (!b->dd_valid) return fail(SWF_E_STATE, "swf_batch_ambiguity_search_selected needs a swf_batch_select_ambiguity_pairs after the last solve");
+    if (!b->tc_valid) return fail(SWF_E_STATE, "swf_batch_ambiguity_search_selected needs a swf_batch_tail_covariance after the last solve");
+    const int nw = (int)b->win.size();
+    int nmax = 1;                // a window appends at most one pair per tail coordinate (each pair marks a new coordinate used)
+    for (int w = 0; w < nw; w++) nmax = std::max(nmax, std::min(b->hw[w].tail_dim, (int)SWF_LAMBDA_NMAX));
+    LambdaArgs A{};
+    A.n_prob = nw; A.ld = SWF_LAMBDA_NMAX; A.m = 2; A.ldl = nmax | 1;
+    A.pair_first = b->am_first; A.pairs = b->am_pairs; A.pair_count = b->dd_npair;
+    A.tcQ = b->tc_Q; A.tc_ld = b->tc_ld; A.tc_n = b->tc_tail; A.tc_rank = b->tc_rank; A.x = b->D.x;
+    A.rec = b->am_rec; A.rec_ld = LBD_REC_QB + nmax * nmax; A.thr = ratio_threshold;
+    b->am_valid = false; b->fx_valid = false;
+    const int rc = swf_internal_lambda_launch(A, true, b->stream);
+    if (rc) return rc;
+    b->am_nb.assign((size_t)nw, 0); b->am_rec_ld = A.rec_ld;          // the counts are on the device: filled when the host first reads them
+    b->am_valid = true; b->am_host = false; b->am_selected = true; b->am_sel_host = false;
+    return SWF_OK;
+}
+
+// after a selected search: the pairs and the counts the search ran on, as swf_batch_ambiguity_search would have staged them
+static int am_selected_fetch(swf_batch* b) {
+    if (b->am_sel_host) return SWF_OK;
+    const int rc = dd_fetch(b);              // (a selection newer than the search would have invalidated the search)
+    if (rc) return rc;
+    const int nw = (int)b->win.size();
+    b->am_h_first.resize((size_t)nw + 1); b->am_h_pairs.assign((size_t)nw * SWF_LAMBDA_NMAX, make_int4(0, 0, 0, 0)); b->am_nb.assign((size_t)nw, 0);
+    for (int w = 0; w <= nw; w++) b->am_h_first[(size_t)w] = w * SWF_LAMBDA_NMAX;
+    for (int w = 0; w < nw; w++) {
+        const int* c = b->dd_h_counts.data() + (size_t)w * 4;
+        const int n = c[3] == SWF_DDSEL_OK ? c[0] : 0;
+        b->am_nb[(size_t)w] = n;
+        const HostWin& h = b->hw[w];
+        for (int i = 0; i < n; i++) {
+            const int* q = b->dd_h_pairs.data() + ((size_t)w * SWF_LAMBDA_NMAX + i) * 2;
+            b->am_h_pairs[(size_t)w * SWF_LAMBDA_NMAX + i] = make_int4(q[0], q[1], h.tail_x[(size_t)q[0]], h.tail_x[(size_t)q[1]]);
+        }
+    }
+    b->am_sel_host = true;
     return SWF_OK;
 }
 
@@ -1300,7 +1471,7 @@ extern "C" int swf_batch_get_ambiguity_fix(swf_batch* b, int32_t w, double* F, d
         b->am_host = true;
     }
     const double* r = b->h_am.data() + (size_t)w * b->am_rec_ld;
-    const size_t n = (size_t)b->am_nb[w];
+    const size_t n = b->am_selected ? (size_t)r[LBD_REC_INFO + 2] : (size_t)b->am_nb[w];      // a selected search: the count is the device's
     if (n_b) *n_b = (int32_t)n;
     if (F) for (int j = 0; j < 2; j++) memcpy(F + j * n, r + LBD_REC_F + j * SWF_LAMBDA_NMAX, n * sizeof(double));
     if (s) memcpy(s, r + LBD_REC_S, 2 * sizeof(double));
@@ -1320,6 +1491,7 @@ extern "C" int swf_batch_fix_prior(swf_batch* b, const int32_t* prior_sel, const
     if (!b->am_valid) return fail(SWF_E_STATE, "swf_batch_fix_prior needs a swf_batch_ambiguity_search after the last solve");
     if (form != SWF_PRIOR_EIGEN && form != SWF_PRIOR_CHOLESKY) return fail(SWF_E_INVALID, "swf_batch_fix_prior: form must be SWF_PRIOR_EIGEN or SWF_PRIOR_CHOLESKY");
     if (!std::isfinite(istd) || !(istd > 0.0) || !std::isfinite(eps) || eps < 0.0) return fail(SWF_E_INVALID, "swf_batch_fix_prior: istd must be positive and eps non-negative");
+    if (b->am_selected) { const int frc = am_selected_fetch(b); if (frc) return frc; }      // the one synchronisation of the device chain
     const int nw = (int)b->win.size();
     // validated into locals and copied into the batch's staging on success: a refused call leaves the previous call's tables as they were
     std::vector<FixWin> fw((size_t)nw, FixWin{ 0, 0, 0, 0 });

@@ -43,6 +43,8 @@ struct LambdaArgs {
     double* F; double* s; int* info;                         // F [p][m][ld], s [p][m], info [p]
     // BATCH only
     const int* pair_first; const int4* pairs;                // [n_prob + 1]; per pair: tail a, tail b, state index of a, of b
+    const int* pair_count;                                   // null, or (k_lambda<true, true>, the pairs chosen on the device by k_dd_select):
+                                                             // window p owns pair_count[p] pairs at p * LBD_NMAX and pair_first is not read
     const double* tcQ; int tc_ld; const int* tc_n; const int* tc_rank;   // swf_batch_tail_covariance outputs: window p's Qy is
                                                              // tc_n[p] x tc_n[p] row-major at tcQ + p tc_ld^2
     const double* x;                                         // the device state
@@ -50,7 +52,7 @@ struct LambdaArgs {
     double thr;
 };
 
-// enqueue k_lambda<batch> for A.n_prob problems on stream st (swf_lambda.hip)
+// enqueue k_lambda<batch> (k_lambda<true, true> when batch and A.pair_count is set) for A.n_prob problems on stream st (swf_lambda.hip)
 int swf_internal_lambda_launch(const LambdaArgs& A, bool batch, hipStream_t st);
 
 #ifdef SWF_LAMBDA_DEVICE_BODY
@@ -88,7 +90,8 @@ __device__ __forceinline__ double lbd_qb(const double* Qy, int ld, int4 pr, int4
     return Qy[(size_t)pr.x * ld + pc.x] - Qy[(size_t)pr.x * ld + pc.y] - Qy[(size_t)pr.y * ld + pc.x] + Qy[(size_t)pr.y * ld + pc.y];
 }
 
-template <bool BATCH>
+// SEL (with BATCH) only changes where the window's pairs are found; k_lambda<true> is compiled from the same text as before it existed.
+template <bool BATCH, bool SEL = false>
 __global__ void __launch_bounds__(64) k_lambda(LambdaArgs A) {
 #pragma clang fp contract(off)
     extern __shared__ double lbd_lds[];
@@ -106,8 +109,8 @@ __global__ void __launch_bounds__(64) k_lambda(LambdaArgs A) {
 
     // ---------------------------------------------------------------- operands
     if (BATCH) {
-        f0 = A.pair_first[p];
-        n = A.pair_first[p + 1] - f0;
+        if (SEL) { f0 = p * LBD_NMAX; n = A.pair_count[p]; }
+        else { f0 = A.pair_first[p]; n = A.pair_first[p + 1] - f0; }
         if (n < 1 || n > LBD_NMAX || n > ldl || A.tc_rank[p] < 0) {
             status = SWF_LAMBDA_NO_INPUT;
             if (n >= 1 && n <= LBD_NMAX && n <= ldl && l < n) {          // no valid tail covariance: Qb and bf read back as zeros

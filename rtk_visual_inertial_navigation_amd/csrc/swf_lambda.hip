@@ -1,5 +1,6 @@
 // swf_lambda.hip — k_lambda (swf_lambda.h) instantiated for the stand-alone operator swf_lambda_batch and for the batch
-// engine's swf_batch_ambiguity_search (swf_engine.hip), which share one body.  gfx950 only, no CPU path.
+// engine's swf_batch_ambiguity_search and swf_batch_ambiguity_search_selected (swf_engine.hip), which share one body.  gfx950 only,
+// no CPU path.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <string>
@@ -13,10 +14,12 @@ static int lbd_fail(int code, const std::string& m) { swf_internal_set_error(m);
 int swf_internal_lambda_launch(const LambdaArgs& A, bool batch, hipStream_t st) {
     if (A.n_prob <= 0) return SWF_OK;
     const size_t lds = (size_t)2 * A.ldl * A.ldl * sizeof(double);
-    const void* fn = batch ? (const void*)k_lambda<true> : (const void*)k_lambda<false>;
+    const bool sel = batch && A.pair_count;
+    const void* fn = sel ? (const void*)k_lambda<true, true> : batch ? (const void*)k_lambda<true> : (const void*)k_lambda<false>;
     if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return lbd_fail(SWF_E_NODEVICE, "k_lambda: cannot raise the LDS limit");
-    if (batch) hipLaunchKernelGGL(k_lambda<true>, dim3(A.n_prob), dim3(64), lds, st, A);
+    if (sel) hipLaunchKernelGGL((k_lambda<true, true>), dim3(A.n_prob), dim3(64), lds, st, A);
+    else if (batch) hipLaunchKernelGGL(k_lambda<true>, dim3(A.n_prob), dim3(64), lds, st, A);
     else hipLaunchKernelGGL(k_lambda<false>, dim3(A.n_prob), dim3(64), lds, st, A);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lbd_fail(SWF_E_NODEVICE, std::string("k_lambda: ") + hipGetErrorString(e));

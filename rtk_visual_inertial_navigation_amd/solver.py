@@ -61,6 +61,7 @@ EXPORTED = [
     "swf_prior_fix_batch", "swf_batch_fix_prior", "swf_batch_get_fixed_prior", "swf_batch_install_fixed_prior", "swf_problem_fix_prior",
     "swf_phase_screen_batch",
     "swf_gnss_epoch_solve_batch",
+    "swf_dd_select_batch", "swf_batch_select_ambiguity_pairs", "swf_batch_ambiguity_search_selected", "swf_batch_get_ambiguity_pairs",
 ]
 
 
@@ -234,6 +235,53 @@ class BatchSolver:
                                                    C.byref(fx), Qb.ctypes.data_as(_pd), bf.ctypes.data_as(_pd), C.byref(nb), C.byref(info)),
                  "swf_batch_get_ambiguity_fix")
             out.append(dict(F=F, s=sv, ratio=r, fixed=bool(fx.value), Qb=Qb, bf=bf, n_b=nb.value, info=info.value))
+        return out
+
+    def _ambiguity_fix(self, w, k):
+        F, sv, r, Qb, bf = np.zeros((2, k)), np.zeros(2), np.zeros(2), np.zeros((k, k)), np.zeros(k)
+        fx, nb, info = C.c_int32(), C.c_int32(), C.c_int32()
+        _chk(lib().swf_batch_get_ambiguity_fix(self._h, C.c_int32(w), F.ctypes.data_as(_pd), sv.ctypes.data_as(_pd), r.ctypes.data_as(_pd),
+                                               C.byref(fx), Qb.ctypes.data_as(_pd), bf.ctypes.data_as(_pd), C.byref(nb), C.byref(info)),
+             "swf_batch_get_ambiguity_fix")
+        return dict(F=F, s=sv, ratio=r, fixed=bool(fx.value), Qb=Qb, bf=bf, n_b=nb.value, info=info.value)
+
+    def select_ambiguity_pairs(self, epochs_per_window, gate):
+        """The double-difference pairs of the search chosen on the device (FindReferenceSatellites and LambdaSearch's D3 loop,
+        R/swf/swf_lambda.cpp:8-53, 118-188) from the device state, after a solve; asynchronous.  epochs_per_window[w] = the window's
+        epochs NEWEST FIRST, each a list of (class = sys * 2 + f, tail coordinate) in the reference's observation order; gate: one
+        value or one per window (the reference: 0.2 after a fix, 1.4 otherwise).  Read the result with ambiguity_pairs(w)."""
+        if len(epochs_per_window) != self.n:
+            raise ValueError("select_ambiguity_pairs: one epoch list per window")
+        ef, of, obs = _dd_flatten(epochs_per_window)
+        g = np.ascontiguousarray(np.broadcast_to(np.asarray(gate, np.float64), (self.n,)))
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_batch_select_ambiguity_pairs(self._h, ef.ctypes.data_as(pi), of.ctypes.data_as(pi), obs.ctypes.data_as(pi), g.ctypes.data_as(_pd)),
+             "swf_batch_select_ambiguity_pairs")
+        self._dd_shape = [(len(ep), sum(len(e) for e in ep)) for ep in epochs_per_window]
+
+    def ambiguity_pairs(self, w=0):
+        """Window w's selection (synchronises): dict(pairs [n_pairs][2], raw_pairs [64][2] with -1 behind the pairs, n_pairs,
+        last_count, last_ref_count, info (DDSEL_*), refs [epochs][6], cost [observations], role [observations])."""
+        ne, no = self._dd_shape[w] if getattr(self, "_dd_shape", None) else (0, 0)
+        pairs, counts = np.zeros((LAMBDA_NMAX, 2), np.int32), np.zeros(4, np.int32)
+        refs, cost, role = np.zeros((max(ne, 1), 6), np.int32), np.zeros(max(no, 1)), np.zeros(max(no, 1), np.uint8)
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_batch_get_ambiguity_pairs(self._h, C.c_int32(w), pairs.ctypes.data_as(pi), counts.ctypes.data_as(pi), refs.ctypes.data_as(pi),
+                                                 cost.ctypes.data_as(_pd), role.ctypes.data_as(C.POINTER(C.c_uint8))), "swf_batch_get_ambiguity_pairs")
+        return _dd_result(pairs, counts, refs[:ne], cost[:no], role[:no])
+
+    def ambiguity_search_selected(self, ratio_threshold=2.0, fetch=True):
+        """ambiguity_search() on the pairs select_ambiguity_pairs() chose, without leaving the device: needs a selection and a
+        tail_covariance() after the last solve.  A window whose selection is not DDSEL_OK reports LAMBDA_NO_INPUT.  fetch = False only
+        enqueues; otherwise one dict per window as ambiguity_search() returns."""
+        _chk(lib().swf_batch_ambiguity_search_selected(self._h, C.c_double(ratio_threshold)), "swf_batch_ambiguity_search_selected")
+        if not fetch:
+            return None
+        out = []
+        for w in range(self.n):
+            nb = C.c_int32()
+            _chk(lib().swf_batch_get_ambiguity_fix(self._h, C.c_int32(w), None, None, None, None, None, None, C.byref(nb), None), "swf_batch_get_ambiguity_fix")
+            out.append(self._ambiguity_fix(w, nb.value))
         return out
 
     def fix_prior(self, prior_sel=None, n_use=None, enable=None, ignore_ratio=False, scalars_at_zero=True, istd=1.0 / 0.03, eps=1e-8, form=0):
@@ -836,6 +884,10 @@ def triangulate_batch(Ps, Rs, tic, ric, pbg, start_frame, pt0, pt1, init_depth=5
 
 
 LAMBDA_OK, LAMBDA_NOT_PD, LAMBDA_LOOP_LIMIT, LAMBDA_NO_INPUT = 0, 1, 2, 3
+LAMBDA_NMAX = 64
+DDSEL_NMAX, DDSEL_TMAX = 256, 2048
+DDSEL_OK, DDSEL_TOO_FEW, DDSEL_OVERFLOW, DDSEL_NONFINITE = 0, 1, 2, 3
+DDSEL_SKIPPED, DDSEL_REFERENCE, DDSEL_PAIRED, DDSEL_GATED_OUT, DDSEL_NO_REFERENCE = 0, 1, 2, 3, 4
 FEAT_OUTLIER, FEAT_NEG_DEPTH, FEAT_UNOBSERVED = 1, 2, 4
 
 
@@ -857,6 +909,50 @@ def lambda_batch(a_list, Q_list, m=2):
                                 C.c_int32(m), F.ctypes.data_as(_pd), s.ctypes.data_as(_pd), info.ctypes.data_as(pi), C.c_int32(0), None),
          "swf_lambda_batch")
     return [(F[p, :, :ns[p]].copy(), s[p].copy(), int(info[p])) for p in range(P)]
+
+
+def _dd_flatten(epochs_per_window):
+    """epoch_first [W + 1], obs_first [E + 1], obs [n][2] of a list (windows) of lists (epochs, newest first) of (class, t)."""
+    ef, of, obs = [0], [0], []
+    for ep in epochs_per_window:
+        for e in ep:
+            obs.extend((int(c), int(t)) for c, t in e)
+            of.append(len(obs))
+        ef.append(len(of) - 1)
+    o = np.array(obs, np.int32).reshape(-1, 2) if obs else np.zeros((1, 2), np.int32)
+    return np.array(ef, np.int32), np.array(of, np.int32), np.ascontiguousarray(o)
+
+
+def _dd_result(pairs, counts, refs, cost, role):
+    n = int(counts[0])
+    return dict(pairs=pairs[:n].copy(), raw_pairs=pairs.copy(), n_pairs=n, last_count=int(counts[1]), last_ref_count=int(counts[2]),
+                info=int(counts[3]), refs=refs.copy(), cost=cost.copy(), role=role.copy())
+
+
+def dd_select_batch(epochs_per_window, y_list, gate):
+    """The double-difference pairs of the integer ambiguity search (FindReferenceSatellites and LambdaSearch's D3 loop,
+    R/swf/swf_lambda.cpp:8-53, 118-188) for a batch of windows on the device (swf_dd_select_batch, which see).
+    epochs_per_window[w] = the window's epochs NEWEST FIRST, each a list of (class = sys * 2 + f, tail coordinate) in the reference's
+    observation order; y_list[w] = the float values of the window's tail; gate: one value or one per window.  Returns one dict per
+    window as BatchSolver.ambiguity_pairs()."""
+    W = len(epochs_per_window)
+    if len(y_list) != W:
+        raise ValueError("dd_select_batch: one y per window")
+    ef, of, obs = _dd_flatten(epochs_per_window)
+    ys = [np.asarray(v, np.float64).ravel() for v in y_list]
+    yf = np.zeros(W + 1, np.int32)
+    yf[1:] = np.cumsum([v.size for v in ys])
+    y = np.ascontiguousarray(np.concatenate(ys + [np.zeros(1)]))
+    g = np.ascontiguousarray(np.broadcast_to(np.asarray(gate, np.float64), (W,))) if W else np.zeros(1)
+    E, n = int(ef[-1]), int(of[-1])
+    pairs, counts = np.full((max(W, 1), LAMBDA_NMAX, 2), -2, np.int32), np.full((max(W, 1), 4), -2, np.int32)
+    refs, cost, role = np.full((max(E, 1), 6), -2, np.int32), np.full(max(n, 1), -2.0), np.full(max(n, 1), 255, np.uint8)
+    pi = C.POINTER(C.c_int32)
+    _chk(lib().swf_dd_select_batch(C.c_int32(W), ef.ctypes.data_as(pi), of.ctypes.data_as(pi), obs.ctypes.data_as(pi), yf.ctypes.data_as(pi),
+                                   y.ctypes.data_as(_pd), g.ctypes.data_as(_pd), pairs.ctypes.data_as(pi), counts.ctypes.data_as(pi),
+                                   refs.ctypes.data_as(pi), cost.ctypes.data_as(_pd), role.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                   C.c_int32(0), None), "swf_dd_select_batch")
+    return [_dd_result(pairs[w], counts[w], refs[ef[w]:ef[w + 1]], cost[of[ef[w]]:of[ef[w + 1]]], role[of[ef[w]]:of[ef[w + 1]]]) for w in range(W)]
 
 
 FIX_PRIOR_MAXN = 140
