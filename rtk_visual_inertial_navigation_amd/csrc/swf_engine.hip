@@ -266,6 +266,8 @@ struct swf_batch {
     int asm_programs = 0;                 // distinct assembly programs of the batch (windows of identical structure share one)
     int ls_qpb = 1, ls_var = 0, ls_kms = 8; bool ls_folded = false, s_direct = false;     // k_lm_schur launch shape, fixed at creation (the pair lists depend on it)
     bool full_final = false;              // SWF_FULL_FINAL_ELIM=1: the solve's final linearisation runs the complete group-0 elimination, as every other one does (parity: bit-identical to the gradient-only pass)
+    bool no_clq_pack = false;             // SWF_NO_CLIQUE_PACK=1: class 0 as one wavefront per clique (k_clique_elim<48,32,1,0>) instead of two cliques per wavefront (k_clique_pack) (parity, A/B: bit-identical)
+    int clp_rows = 1, clp_ld = 3;         // k_clique_pack: rows and leading dimension of its LDS Jacobians (the largest class-0 clique of the batch)
     int ls_gqpb = 4;                      // landmark parts per workgroup of the gradient-only landmark pass (it has no ring to fill: chosen for occupancy, not by ls_qpb)
     int timing = 0;                       // bitmask of SWF_K_* brackets
     swf_timing last{};
@@ -305,12 +307,14 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
     b->no_step_fuse = getenv("SWF_NO_STEP_FUSE") != nullptr;
     b->no_decide_fuse = getenv("SWF_NO_DECIDE_FUSE") != nullptr;
     b->full_final = getenv("SWF_FULL_FINAL_ELIM") != nullptr;
+    b->no_clq_pack = getenv("SWF_NO_CLIQUE_PACK") != nullptr;
     // what the launcher reads of the plan
     b->max_tiles = B.max_tiles; b->max_prior_dim = B.max_prior_dim; b->max_red = B.max_red; b->min_red = B.min_red;
     b->rr_nmax = B.rr_nmax; b->rr4_has15 = B.rr4_has15; b->rr4_has16 = B.rr4_has16; b->n_pch_split = B.n_pch_split;
     b->lat_fuse = B.lat_fuse; b->asm_programs = B.asm_programs;
     b->ls_qpb = B.ls_qpb; b->ls_var = B.ls_var; b->ls_kms = B.ls_kms; b->ls_gqpb = B.ls_gqpb; b->ls_folded = B.ls_folded; b->s_direct = B.s_direct;
     for (int k = 0; k < 5; k++) b->clc_imu[k] = B.clc_imu[k];
+    b->clp_rows = B.clp_rows; b->clp_ld = B.clp_ld;
     b->n_comp = B.n_comp; b->comp_nmax = B.comp_nmax; b->comp_nmin = B.comp_nmin; b->comp_ne = B.comp_ne;
     b->jac_bytes = B.jac_bytes; b->proj_bytes = B.proj_bytes; b->chol_flops = B.chol_flops;
     b->lm_schur_flops = B.lm_schur_flops; b->lm_schur_flops_sym = B.lm_schur_flops_sym; b->lm_schur_mfma = B.lm_schur_mfma;
@@ -755,8 +759,17 @@ struct Launcher {
             }
             if (D.n_clc[0]) {
                 Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(0));
-                if (grad) hipLaunchKernelGGL((k_clique_elim<48, 32, 1, 0, true>), dim3(D.n_clc[0]), dim3(64), 0, cstream(0), D, O);
-                else hipLaunchKernelGGL((k_clique_elim<48, 32, 1, 0>), dim3(D.n_clc[0]), dim3(64), 0, cstream(0), D, O);
+                // two cliques per wavefront, LDS for the batch's largest class-0 clique (two halves of Jc | rv | Me | T | Ei | Eg)
+                // (one wavefront per workgroup: four independent ones measured slower, 29.4 against 25.7 us per launch: profiles/r09)
+                constexpr int CLP_NW = 1;
+                const size_t lds = CLP_NW * 2 * ((size_t)(b->clp_rows + 2) * b->clp_ld + b->clp_rows + 2) * sizeof(double);
+                const dim3 cgrid(((D.n_clc[0] + 1) / 2 + CLP_NW - 1) / CLP_NW);
+                if (b->no_clq_pack) {
+                    if (grad) hipLaunchKernelGGL((k_clique_elim<48, 32, 1, 0, true>), dim3(D.n_clc[0]), dim3(64), 0, cstream(0), D, O);
+                    else hipLaunchKernelGGL((k_clique_elim<48, 32, 1, 0>), dim3(D.n_clc[0]), dim3(64), 0, cstream(0), D, O);
+                }
+                else if (grad) hipLaunchKernelGGL((k_clique_pack<true, CLP_NW>), cgrid, dim3(64 * CLP_NW), lds, cstream(0), D, O, b->clp_rows, b->clp_ld);
+                else hipLaunchKernelGGL((k_clique_pack<false, CLP_NW>), cgrid, dim3(64 * CLP_NW), lds, cstream(0), D, O, b->clp_rows, b->clp_ld);
             }
             if (D.n_clc[2] && !clq_fused) {
                 Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(2));

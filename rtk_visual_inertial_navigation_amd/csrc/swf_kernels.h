@@ -1011,7 +1011,8 @@ __device__ unsigned long long g_clq_stamps[16];
 #define QST(i)
 #endif
 // size classes (host-assigned): 0 = d_e<=1, <=48 rows, <=32 cols (receiver clocks, dummy, small free groups);
-// 1 = <=32 rows, <=48 cols (speed-bias cliques); 2 = up to 64 x 64.
+// 1 = <=32 rows, <=48 cols (speed-bias cliques); 2 = up to 64 x 64.  (Class 0 runs two cliques per wavefront: k_clique_pack below;
+// its instantiation of this function is the reference behind SWF_NO_CLIQUE_PACK.)
 // ONE WAVEFRONT PER CLIQUE (the kernel is latency-bound: what matters is how many cliques a CU keeps in flight).
 // The wave is synchronous with itself, so the phases need no workgroup barriers, and M_ff is never stored:
 // every lane forms 2x2 blocks of M_ff = J_f^T J_f in registers and applies the Schur correction in place.
@@ -1291,6 +1292,180 @@ __global__ void __launch_bounds__(256) k_clique_elim4(DevBatch B, DevOpt O) { d_
 // columns: N <= 18 ambiguities fit 96 rows x 64 columns, more take k_clique_big).  The four-wave form of the same function.
 template <bool GRAD = false>
 __global__ void __launch_bounds__(256) k_clique_tall(DevBatch B, DevOpt O) { d_clique_elim<CLQ_TALLR, 64, 9, 4, 8, 4, 4, GRAD>(B, O, (int)blockIdx.x); }
+
+// Class 0 on the batch path, PACKED: two cliques per wavefront.  A class-0 clique has d_e <= 1 and d <= 32 columns (the bench's receiver
+// clocks: 20 rows x 17 columns), so one wavefront per clique leaves two thirds of its lanes idle and — with LDS declared for the class
+// envelope — 12 cliques on a CU.  Here lanes 0-31 take clique 2i and lanes 32-63 clique 2i + 1 of clc_rec[0], "lane" below is the lane
+// within the half (hl), and the LDS is dynamic, sized by the largest n_rows (R) and d of the BATCH's class-0 cliques (LD = (d + 2) | 1:
+// two zero pad columns behind d and odd, Plan::clp_rows / clp_ld).  Per half, in doubles: Jc[R][LD] | rv[R] | Me[LD] | T[LD] | Ei | Eg.
+// The arithmetic is d_clique_elim<48, 32, 1, 0>'s: every output element is formed by ONE lane from the same operands in the same order
+// (k-ascending dot products, the d_e = 1 pivot with rcp + two Newton steps, T, Eg, cs, the elements of C as k-ascending sums with the Me / T
+// correction behind them), so the two forms give the same bits (tests/test_clique_pack_gpu.py).  Pivot-row broadcasts come from the half's
+// own lane 0 (v_readlane of lanes 0 and 32, selected by half).  What is wave-uniform there is per-half predication here: the index
+// past the last clique, need_lin, d_e == 0, a failed pivot (its half raises lin_fail and writes nothing further; the other half goes on).
+// Loops over rows / blocks / gather rounds are wave-uniform up to the larger bound of the two halves, each half predicated on its own.
+// The wave is synchronous with itself: wave-level fences, no workgroup barrier.
+__device__ __forceinline__ double readhalf_d(double v, bool upper) { double a = readlane_d(v, 0), b = readlane_d(v, 32); return upper ? b : a; }
+// NW: wavefronts per workgroup, each with a pair of its own and its own slice of the LDS (they share nothing and never meet at a barrier).
+template <bool GRAD, int NW>
+__global__ void __launch_bounds__(64 * NW) k_clique_pack(DevBatch B, DevOpt O, const int R, const int LD) {
+    constexpr int PF = 12;                           // values per lane and round of the gather (the bench's 340 values: one round of 32 x 12)
+    extern __shared__ double clp_lds[];
+    const int lane = threadIdx.x & 63, hl = lane & 31, pair = (int)blockIdx.x * NW + (NW > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0);
+    const bool up = lane >= 32;
+    double* Jc = clp_lds + (2 * (pair - (int)blockIdx.x * NW) + (up ? 1 : 0)) * ((R + 2) * LD + R + 2);
+    double* rv = Jc + R * LD; double* Me = rv + R; double* T = Me + LD; double* Ei = T + LD; double* Eg = Ei + 1;
+    const int n = B.n_clc[0];
+    int cidx = 2 * pair + (up ? 1 : 0);
+    bool act = cidx < n;
+    const Clique& C = B.clc_rec[0][act ? cidx : 0];
+    WinState& s = B.ws[C.win];
+    act = act && s.need_lin;
+    if (__builtin_amdgcn_ballot_w64(act) == 0) return;
+    // (a half that sits out has no rows and no columns: every predicate below is false for it)
+    const int de = act ? C.d_e : 0, df = act ? C.d_f : 0, d = de + df, nrow = act ? C.n_rows : 0, tot = nrow * d;
+    const int nrow_m = max(__builtin_amdgcn_readlane(nrow, 0), __builtin_amdgcn_readlane(nrow, 32));
+    const int tot_m = max(__builtin_amdgcn_readlane(tot, 0), __builtin_amdgcn_readlane(tot, 32));
+    {
+        const double* gJ = B.g_J + C.j_off;
+        float rd = 1.0f / (float)(nrow > 0 ? nrow : 1);
+        // residual rows (n_rows <= 48: two per lane), requested ahead of the Jacobian and stored behind it: one exposed round trip for both
+        const double r0 = hl < nrow ? B.g_r[C.r_off + hl] : 0.0, r1 = hl + 32 < nrow ? B.g_r[C.r_off + hl + 32] : 0.0;
+        for (int k = hl; k < nrow; k += 32) { Jc[k * LD + d] = 0.0; Jc[k * LD + d + 1] = 0.0; }       // zero pad columns (3x3 tiles)
+        for (int base = 0; base < tot_m; base += PF * 32) {
+            double v[PF];
+#pragma unroll
+            for (int u = 0; u < PF; u++) { int e = base + u * 32 + hl; v[u] = e < tot ? gJ[e] : 0.0; }
+#pragma unroll
+            for (int u = 0; u < PF; u++) {
+                int e = base + u * 32 + hl;
+                int col = (int)((e + 0.5f) * rd);                                    // exact floor(e / nrow) for e < 4096, nrow <= 64
+                col += (e - col * nrow >= nrow) ? 1 : 0; col -= (e - col * nrow < 0) ? 1 : 0;
+                if (e < tot) Jc[(e - col * nrow) * LD + col] = v[u];
+            }
+        }
+        if (hl < nrow) rv[hl] = r0;
+        if (hl + 32 < nrow) rv[hl + 32] = r1;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    // lane c < d: column c of M_e* (one row: d_e <= 1), g_c and M_cc, k-ascending
+    double me = 0, gc = 0, mcc = 0;
+    {
+        const int c = hl < d ? hl : 0;
+#pragma unroll 4
+        for (int k = 0; k < nrow_m; k++) {
+            if (k < nrow) {
+                double x = Jc[k * LD + c];
+                gc += x * rv[k]; mcc += x * x;
+                if (!GRAD) me += Jc[k * LD] * x;
+            }
+        }
+    }
+    if (hl < d) {
+        if (!GRAD) Me[hl] = 0 < de ? me : 0.0;
+        if (hl < de) { B.g[C.e_loc + hl] = gc; B.diag[C.e_loc + hl] = mcc; B.vc[C.e_loc + hl] = gc / clampd(mcc, O.min_diag, O.max_diag); }
+        else { B.cv_graw[C.v_off + hl - de] = gc; B.cv_dgraw[C.v_off + hl - de] = mcc; }
+    }
+    if (GRAD) return;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    bool go = act;                                   // (cleared by a failed pivot: the half writes nothing below)
+    {
+        // [M_ee + mu D | 1] -> [1 | Einv]: the d_e = 1 step of the Gauss-Jordan, the row on the half's lane 0
+        double row[2];
+        {
+            double v = hl < de ? Me[hl] : 0.0;
+            if (hl == 0 && de > 0) v += s.mu * damp_diag(O, v, B.jsc + C.e_loc + hl, s.iter == 0);
+            row[0] = v; row[1] = (hl == 0) ? 1.0 : 0.0;
+        }
+        double piv = readhalf_d(row[0], up);
+        const bool bad = de > 0 && !(piv > 0.0);
+        double ip = __builtin_amdgcn_rcp(piv);
+        ip = ip * (2.0 - piv * ip); ip = ip * (2.0 - piv * ip);
+        double aik = row[0];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            double akj = readhalf_d(row[j], up) * ip;
+            row[j] = (hl == 0) ? akj : row[j] - aik * akj;
+        }
+        if (bad) { if (hl == 0) s.lin_fail = 1; go = false; }
+        if (hl == 0) Ei[0] = de > 0 ? row[1] : 0.0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    // lane j < d_f: T_j = Einv M_ef_j; lane 0: Eg = Einv g_e.  (d_e == 0: Me, Ei and with them T are zeros, as the one-clique form keeps them)
+    {
+        const int j = hl < df ? hl : 0;
+        double sv = 0, sg = 0, ev = Ei[0];
+        sv += ev * Me[de + j]; sg += ev * readhalf_d(gc, up);
+        if (hl < LD) T[hl] = hl < df ? sv : 0.0;
+        if (hl == 0) Eg[0] = de > 0 ? sg : 0.0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    if (go) {
+        if (de > 0) {
+            double* E = B.cE + C.e_off;
+            if (hl == 0) E[0] = Ei[0];
+            if (hl < df) E[de * de + hl] = Me[de + hl];
+            if (hl < de) E[de * de + de * df + hl] = gc;
+        }
+        // cs_j = -(M_fe Eg)_j
+        if (hl < df) {
+            double v = 0;
+            if (de > 0) v -= Me[de + hl] * Eg[0];
+            B.cv_cs[C.v_off + hl] = v;
+        }
+    }
+    // C = M_ff - M_fe T in 3x3 tiles of the lower triangle, one tile per lane and pass: six LDS operands per row for nine sums (the 2x2
+    // blocks of the one-clique form read sixteen for eight, two blocks per lane, and the LDS pipe is what this phase waits for).  An element
+    // (i, j), i >= j, is the same k-ascending sum of x_i x_j with the same correction Me_i T_j behind it: the same bits.
+    double* Cm = B.C + C.C_off;
+    {
+        const int nb = (df + 2) / 3, ntile = go ? nb * (nb + 1) / 2 : 0;
+        const int ntile_m = max(__builtin_amdgcn_readlane(ntile, 0), __builtin_amdgcn_readlane(ntile, 32));
+        for (int t0 = hl; t0 - hl < ntile_m; t0 += 32) {
+            const bool on = t0 < ntile;
+            const int t = on ? t0 : 0;
+            int ba = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
+            while ((ba + 1) * (ba + 2) / 2 <= t) ba++;
+            while (ba * (ba + 1) / 2 > t) ba--;
+            const int bb = t - ba * (ba + 1) / 2, i0 = 3 * ba, j0 = 3 * bb;
+            double m[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+#pragma unroll 4
+            for (int k = 0; k < nrow_m; k++) {
+                if (k < nrow) {
+                    double xa[3], xb[3];
+#pragma unroll
+                    for (int q = 0; q < 3; q++) { xa[q] = Jc[k * LD + de + i0 + q]; xb[q] = Jc[k * LD + de + j0 + q]; }
+#pragma unroll
+                    for (int q = 0; q < 3; q++)
+#pragma unroll
+                        for (int r = 0; r < 3; r++) m[q][r] += xa[q] * xb[r];
+                }
+            }
+            {
+                double f[3], tt[3];
+#pragma unroll
+                for (int q = 0; q < 3; q++) { f[q] = Me[de + i0 + q]; tt[q] = T[j0 + q]; }
+#pragma unroll
+                for (int q = 0; q < 3; q++)
+#pragma unroll
+                    for (int r = 0; r < 3; r++) m[q][r] -= f[q] * tt[r];
+            }
+            if (on) {
+#pragma unroll
+                for (int q = 0; q < 3; q++)
+#pragma unroll
+                    for (int r = 0; r < 3; r++) {
+                        const int i = i0 + q, j = j0 + r;
+                        if (i < df && j <= i) { Cm[i * df + j] = m[q][r]; Cm[j * df + i] = m[q][r]; }
+                    }
+            }
+        }
+    }
+}
 
 // Latency path: the landmark Schur complement and the clique eliminations are independent of each other (both follow the factor
 // evaluation, both feed the assembly) — ONE grid of 1024-thread workgroups runs both: rows [0, n_parts) of the grid are k_lm_schur's

@@ -833,6 +833,9 @@ void plan_pair_clique_classes(Plan& B, std::vector<int>& pd, std::vector<int>& p
         for (int i : clc[k]) B.clc_rec[k].push_back(B.cl[i]);
         B.n_clc[k] = (int)clc[k].size();
     }
+    // class 0 runs two cliques per wavefront out of dynamic LDS (k_clique_pack): rows x leading dimension of the largest one (odd, two pad columns)
+    B.clp_rows = 1; B.clp_ld = 3;
+    for (const Clique& c : B.clc_rec[0]) { B.clp_rows = std::max(B.clp_rows, c.n_rows); B.clp_ld = std::max(B.clp_ld, (c.d_e + c.d_f + 2) | 1); }
 }
 
 int plan_asm_programs(Plan& B, const std::vector<int>& pd, const std::vector<int>& po, std::string& err) {
@@ -1178,6 +1181,16 @@ int plan_validate(const Plan& B, std::string& err) {
         }
     }
     for (auto& kv : cl_seen) NEED(kv.second == 1, "clc_rec: a clique in no class, fac0", kv.first[0]);
+    // k_clique_pack's LDS: every class-0 clique inside clp_rows x clp_ld (two pad columns behind its d), the leading dimension odd, the envelope not exceeded
+    NEED(B.clp_rows >= 1 && B.clp_rows <= 48 && B.clp_ld >= 3 && B.clp_ld <= 35 && (B.clp_ld & 1) == 1, "clp_rows", B.clp_rows);
+    {
+        int mr = 1, ml = 3;
+        for (const Clique& C : B.clc_rec[0]) {
+            NEED(C.n_rows <= B.clp_rows && C.d_e + C.d_f + 2 <= B.clp_ld, "clp_ld", &C - B.clc_rec[0].data());
+            mr = std::max(mr, C.n_rows); ml = std::max(ml, (C.d_e + C.d_f + 2) | 1);
+        }
+        NEED(mr == B.clp_rows && ml == B.clp_ld, "clp_rows: not the largest class-0 clique", mr);
+    }
     // ---- per window: back-substitution blocks, the k_lm_schur task table and its masks, pairs, the assembly program, s_tnz
     const int TW = B.ls_var <= 1 ? 2 : 1, NCW = ls_ncw(B.ls_var), TPW = ls_tpw(B.ls_var);
     NEED((long long)B.sch_rec.size() >= ((long long)B.sch_c0.back() + 4 * LS_NB) * 32 && (long long)B.sch_km.size() >= ((long long)B.sch_c0.back() / TW + 2) * B.ls_kms, "sch_rec", B.sch_rec.size());

@@ -102,6 +102,7 @@ struct Plan {
     int ls_qpb = 1, ls_var = 0, ls_kms = 8, ls_gqpb = 4; bool ls_folded = false, s_direct = false;
     bool lat_fuse = false, want_aux = false, want_Linv = false, want_Wk = false;
     bool clc_imu[5] = { false, false, false, false, false };
+    int clp_rows = 1, clp_ld = 3;      // class 0 (k_clique_pack): the largest n_rows, and (largest d + 2) | 1, of the batch's class-0 cliques — the kernel's LDS is sized by them
     int n_pch_split = 0; bool rr4_has15 = false, rr4_has16 = false;
     int n_comp = 0, comp_nmax = 0, comp_nmin = 1 << 30; long long comp_ne = 0;
     int asm_programs = 0;
