@@ -26,6 +26,7 @@
 //   InitialBlackFactor(istd)                    R/factor/initial_factor.h:42-48       -> swf_add_scalar_prior
 //   MarginalizationFactor(info)                 R/factor/marginalization_factor.h:104-110 -> swf_add_linear_prior (from a
 //                                                                                        MarginalizationInfo* or from J, r0, x0)
+//   ImuIntegrate() + IMUProcess()               R/swf/swf_imu.cpp:117-213             -> swf_imu_frame_batch (ImuIntegrate below)
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
@@ -822,6 +823,64 @@ inline bool GnssEpochSolve(Rover& rover, double* pose, double* speed_bias, doubl
         for (int k = 0; k < 3; k++) { pose[k] = out->pos[k]; speed_bias[k] = out->vel[k]; }
         for (int k = 0; k < SWF_GES_CLOCKS; k++) gnss_dt[k] = out->clock[k];
         for (int32_t k = 0; k < n; k++) if (amb[(size_t)k]) *amb[(size_t)k] = out->N[(size_t)k];
+    }
+    return true;
+}
+
+// The IMU front of a frame: SWFOptimization::ImuIntegrate with its IMUProcess calls (R/swf/swf_imu.cpp:117-213) for one frame on the
+// device (swf_imu_frame_batch with one frame; a caller with many streams builds the same arrays and makes one call).
+//   accVector, gyrVector   the vector<pair<double, Vector3d>> pairs GetImuInterval returned (any vector type with operator()(i))
+//   prev_time, cur_time    the previous frame's time (the reference's static current_time on entry) and this frame's
+//   acc_0, gyr_0           the estimator's members on entry; on success they hold the last effective sample, as IMUProcess leaves them
+//   P, R, V                Ps[j], Rs[j], Vs[j] of the new frame j (operator()(i), operator()(i, j)); replaced by the propagated values
+//   Ba, Bg                 Bas[j], Bgs[j]
+//   gyrj_prev              pre_integrations[j - 1]->gyrj;  lever_velocity = (j > 5)
+//   Pbg, g_w               the antenna lever arm and Rwgw * G;  noise = ACC_N, GYR_N, ACC_W, GYR_W
+// On success out->pre is the record IMUFactor(const double*) takes, out->header the frame's headers[] entry (cur_time when the last
+// sample was blended onto it, else the last stamp used) and out->cut the effective samples (SlideWindowFrame's push of interval k+1
+// onto interval k is swf_preintegrate_runs_batch over two such blocks).  Returns false, with out->info = SWF_IMUF_*, where the
+// reference asserts; P, R, V, acc_0, gyr_0 are then untouched.  Frame index 0 is neither pushed nor propagated by the reference: do
+// not call this for it.  The IMU queues, GetImuInterval's popping, headers[] and adding the IMUFactor block stay with the caller.
+struct ImuFrameResult {
+    std::vector<double> pre;                     // SWF_PRE_DOUBLES
+    std::vector<double> cut;                     // [rows][7]: the seed with dt 0, then (dt, acc, gyr) per IMUProcess call
+    int rows = 0, info = -1;
+    double header = 0;
+};
+template <class Pairs, class V3, class M3>
+inline bool ImuIntegrate(const Pairs& accVector, const Pairs& gyrVector, double prev_time, double cur_time, V3& acc_0, V3& gyr_0,
+                         V3& P, M3& R, V3& V, const V3& Ba, const V3& Bg, const V3& gyrj_prev, bool lever_velocity, const V3& Pbg,
+                         const V3& g_w, const double noise[4], ImuFrameResult* out) {
+    if (!out || !noise || accVector.size() != gyrVector.size()) return false;
+    const int32_t n = (int32_t)accVector.size(), first[2] = { 0, n }, flags = lever_velocity ? 1 : 0;
+    std::vector<double> raw((size_t)(n + 1) * 7, 0.0);
+    for (int32_t i = 0; i < n; i++) {
+        raw[(size_t)i * 7] = accVector[(size_t)i].first;
+        for (int k = 0; k < 3; k++) { raw[(size_t)i * 7 + 1 + k] = accVector[(size_t)i].second(k); raw[(size_t)i * 7 + 4 + k] = gyrVector[(size_t)i].second(k); }
+    }
+    const double t01[2] = { prev_time, cur_time };
+    double seed[6], state[21], gp[3], pbg[3], gw[3], pred[15];
+    for (int k = 0; k < 3; k++) {
+        seed[k] = acc_0(k); seed[3 + k] = gyr_0(k); state[k] = P(k); state[12 + k] = V(k); state[15 + k] = Ba(k); state[18 + k] = Bg(k);
+        gp[k] = gyrj_prev(k); pbg[k] = Pbg(k); gw[k] = g_w(k);
+        for (int j = 0; j < 3; j++) state[3 + 3 * k + j] = R(k, j);
+    }
+    out->pre.assign(SWF_PRE_DOUBLES, 0.0); out->cut.assign((size_t)(n + 1) * 7, 0.0); out->rows = 0; out->info = -1;
+    int32_t info = -1;
+    if (swf_imu_frame_batch(raw.data(), first, 1, t01, seed, state, gp, &flags, pbg, gw, noise, out->cut.data(), out->pre.data(), pred,
+                            &info, 0, nullptr) != SWF_OK) return false;
+    out->info = info;
+    if (info != SWF_IMUF_OK) return false;
+    int32_t used = 0;                                        // raw samples used: up to and including the first beyond cur_time
+    while (used < n && raw[(size_t)used * 7] <= cur_time) used++;
+    const bool blended = used < n;
+    used += blended ? 1 : 0;
+    out->rows = used + 1; out->cut.resize((size_t)out->rows * 7);
+    out->header = blended ? cur_time : raw[(size_t)(used - 1) * 7];
+    for (int k = 0; k < 3; k++) {
+        P(k) = pred[k]; V(k) = pred[12 + k];
+        acc_0(k) = out->cut[(size_t)used * 7 + 1 + k]; gyr_0(k) = out->cut[(size_t)used * 7 + 4 + k];
+        for (int j = 0; j < 3; j++) R(k, j) = pred[3 + 3 * k + j];
     }
     return true;
 }

@@ -365,6 +365,49 @@ int swf_batch_timing(swf_batch* b, swf_timing* out);
 int swf_preintegrate_batch(const double* samples, const int32_t* first, int32_t n_intervals, const double* bias,
                            const double noise[4], double* pre, int32_t on_device, void* stream);
 
+/* The same pre-integration over a gather list: interval i is the runs run_first[i] .. run_first[i+1]-1 of `runs`, each an
+ * (offset, count) pair of rows of samples[n_samples][7].  The first row of the interval's first non-empty run seeds acc_0 / gyr_0,
+ * every further row of every run is one push_back; the record is bit-identical to swf_preintegrate_batch on the concatenated rows.
+ * The merged interval of SlideWindowFrame (R/swf/swf.cpp:241-247) is "the rows of interval k, then the rows of interval k+1 without
+ * its seed row": two runs, nothing is copied.
+ *   runs       [run_first[n_intervals]][2]   offset, count (count 0 is allowed)
+ *   run_first  [n_intervals + 1]
+ * Host memory: a negative offset or count, a run beyond n_samples, or decreasing run_first: SWF_E_INVALID.  Device memory: such a
+ * run counts as empty.  on_device as for swf_preintegrate_batch. */
+int swf_preintegrate_runs_batch(const double* samples, int32_t n_samples, const int32_t* runs, const int32_t* run_first,
+                                int32_t n_intervals, const double* bias, const double noise[4], double* pre,
+                                int32_t on_device, void* stream);
+
+/* The IMU front of a frame: SWFOptimization::ImuIntegrate and IMUProcess (R/swf/swf_imu.cpp:117-213) for n_frames independent
+ * frames in one launch: the time-stamped samples are cut to (t0, t1] with the last one blended onto t1, the frame's Ps / Rs / Vs are
+ * propagated with the mid-point rule, and the effective samples are pre-integrated.
+ *   raw        [first[n_frames]][7]  t, acc(3), gyr(3): what GetImuInterval (:82-106) hands over: every sample with t0 < t < t1, then
+ *              the first with t >= t1.  A sample beyond t1 is the last one used; rows after it are ignored.
+ *   first      [n_frames + 1]        sample offsets
+ *   t01        [n_frames][2]         t0 = the previous frame's time (the reference's static current_time on entry), t1 = cur_time
+ *   seed       [n_frames][6]         acc_0, gyr_0 on entry: the last effective sample of the previous frame
+ *   state      [n_frames][21]        the new frame's slot on entry: P(3), R(9, row-major), V(3), ba(3), bg(3)
+ *   gyrj_prev  [n_frames][3]         pre_integrations[j-1]->gyrj
+ *   flags      [n_frames]            bit 0: apply the velocity lever-arm terms (frame index > 5, :124, :173)
+ *   pbg, g_w, noise                  host scalars: the antenna lever arm, Rwgw * G, and ACC_N, GYR_N, ACC_W, GYR_W
+ *   cut        [first[n_frames] + n_frames][7]  frame f owns rows first[f] + f ..: the seed with dt 0, then one (dt, acc, gyr) row per
+ *              IMUProcess call: the layout swf_preintegrate_batch and swf_preintegrate_runs_batch read
+ *   pre        [n_frames][SWF_PRE_DOUBLES]      bit-identical to swf_preintegrate_batch on those rows with the bias of `state`
+ *   pred       [n_frames][15]        P, R, V after the loop and the lever-arm restore
+ *   info       [n_frames]            SWF_IMUF_*, where the reference asserts; a failed frame writes its info and nothing else
+ * dt_i = t_i - t_(i-1) with t_(-1) = t0.  The sample beyond t1 becomes dt_1 = t1 - t_prev with acc / gyr = w1 * previous raw sample +
+ * w2 * this one, w1 = dt_2 / (dt_1 + dt_2), w2 = dt_1 / (dt_1 + dt_2), dt_2 = t - t1.  The rotation update multiplies by what the
+ * reference forms: Eigen's toRotationMatrix of the unnormalised quaternion (1, theta / 2) of Utility::deltaQ: R does not stay
+ * orthonormal, and that is kept.  The reference neither pushes nor propagates for frame index 0 (:196): callers do not pass that frame.
+ * Null pointers or (host memory) decreasing `first`: SWF_E_INVALID.  With host memory the per-frame failures are found before the
+ * device is touched (a call whose frames all fail needs none).  A frame's result does not depend on the other frames of the call.
+ * on_device as for swf_preintegrate_batch. */
+enum { SWF_IMUF_OK = 0, SWF_IMUF_EMPTY = 1, SWF_IMUF_NO_INNER = 2, SWF_IMUF_TIME_ORDER = 3 };
+int swf_imu_frame_batch(const double* raw, const int32_t* first, int32_t n_frames, const double* t01, const double* seed,
+                        const double* state, const double* gyrj_prev, const int32_t* flags, const double pbg[3],
+                        const double g_w[3], const double noise[4], double* cut, double* pre, double* pred, int32_t* info,
+                        int32_t on_device, void* stream);
+
 /* Integer least squares: RTKLIB's lambda(n, m, a, Q, F, s) (R/gnss/src/lambda.cpp:58-235) for a batch of problems, one wavefront
  * each: LtDL factorisation, LAMBDA reduction, MLAMBDA search for the m best integer vectors, with the reference's discrete decisions
  * (ROUND = floor(x + 0.5), the 1e-6 permutation margin, LOOPMAX = 10000 search iterations).  The reduction, unbounded in the

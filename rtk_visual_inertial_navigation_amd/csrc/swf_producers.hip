@@ -20,6 +20,11 @@
 // upper-triangular R with cov = R R^T (the "reverse" Cholesky factor): cov^-1 = R^-T R^-1, so R^-1 is the transposed
 // lower Cholesky factor of cov^-1 — the same matrix the reference forms through an explicit inverse, at eps*sqrt(cond)
 // instead of eps*cond.
+//
+// The same kernel, as a template over the sample source, is also the IMU front of a frame (swf_imu_frame_batch: the sample cut and
+// the mid-point prediction of SWFOptimization::ImuIntegrate / IMUProcess, R/swf/swf_imu.cpp:117-213, ride on the loads of the
+// recursion) and pre-integration over a gather list (swf_preintegrate_runs_batch: SlideWindowFrame's merged interval,
+// R/swf/swf.cpp:241-247, without copying samples).  DESIGN.md 3o.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <string>
@@ -40,7 +45,25 @@ struct PreintArgs {
     double* pre;             // [n_int][SWF_PRE_DOUBLES]
     double acc_n2, gyr_n2, acc_w2, gyr_w2;
     int n_int;
+    // PI_RUNS: an interval is the runs run_first[i] .. run_first[i+1]-1 of `runs`, each (offset, count) into samples[n_samples]
+    const int* runs; const int* run_first; int n_samples;
+    // PI_RAW (swf_imu_frame_batch): samples = raw [sum n][7] t, acc, gyr; an interval is a frame; bias = ba, bg of `state`
+    const double* t01;       // [n_int][2]
+    const double* seed;      // [n_int][6]
+    const double* state;     // [n_int][21] P, R (row-major), V, ba, bg
+    const double* gyrj_prev; // [n_int][3]
+    const int* flags;        // [n_int]
+    double* cut;             // [sum n + n_int][7]
+    double* pred;            // [n_int][15]
+    int* info;               // [n_int]
+    double pbg[3], gw[3];
 };
+
+// where the samples of an interval come from
+enum { PI_CONTIG = 0, PI_RUNS = 1, PI_RAW = 2 };
+
+// the value as the registers hold it: what is stored as a cut row is, bit for bit, what the recursions consume
+__device__ __forceinline__ double pinned(double v) { asm volatile("" : "+v"(v)); return v; }
 
 // broadcast of lane N of each 16-lane row to the whole row (DPP row_newbcast)
 template <int N>
@@ -77,15 +100,64 @@ __device__ __forceinline__ void apply_F(const StepMats& S, double* x) {
 #define PI_GROUPS 4            // intervals per wavefront (16 lanes each: lane c < 15 owns column c of the Jacobian and of the covariance)
 #define PI_TLD 17              // padded row of the transpose buffer
 
+// The cursor of PI_RUNS: row after row of run after run.  next() is called only while rows are left, so it ends inside the list; a
+// run that leaves samples[n_samples] counts as empty.
+struct RunCursor {
+    const int* runs; int r, p, cnt, n_samples; long long off;
+    __device__ __forceinline__ static int sane(int off, int cnt, int n_samples) {
+        return (off < 0 || cnt < 0 || (long long)off + cnt > n_samples) ? 0 : cnt;
+    }
+    __device__ __forceinline__ long long next() {
+        p++;
+        while (p >= cnt) { r++; off = runs[2 * r]; cnt = sane(runs[2 * r], runs[2 * r + 1], n_samples); p = 0; }
+        return off + p;
+    }
+};
+
+// One template for the three sample sources; the recursion below the fetch is the same text for all of them, and SRC = PI_CONTIG is
+// swf_preintegrate_batch's kernel as it was.
+//   PI_RUNS  the rows of a gather list (swf_preintegrate_runs_batch).
+//   PI_RAW   time-stamped rows (swf_imu_frame_batch): each fetched row is turned into the effective (dt, acc, gyr) of
+//            SWFOptimization::ImuIntegrate (R/swf/swf_imu.cpp:129-170) on the fly, stored as a cut row, and drives, besides the
+//            pre-integration, the mid-point propagation of IMUProcess (:202-208), redundantly in the 16 lanes of the frame.
+template <int SRC>
 __global__ void __launch_bounds__(64) k_preintegrate(PreintArgs A) {
     __shared__ double sT[PI_GROUPS][15 * PI_TLD];
     const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
     const int it = blockIdx.x * PI_GROUPS + g;
     const bool live = it < A.n_int;
     const int itc = live ? it : A.n_int - 1;
-    const int s0 = A.first[itc], n = live ? A.first[itc + 1] - s0 : 0;
+    int s0 = 0, n = 0;
+    RunCursor rc{};
+    int code = 0;                                           // PI_RAW: SWF_IMUF_*
+    double t1 = 0, tprev = 0;
+    if constexpr (SRC == PI_CONTIG) { s0 = A.first[itc]; n = live ? A.first[itc + 1] - s0 : 0; }
+    if constexpr (SRC == PI_RUNS) {
+        const int r0 = A.run_first[itc], r1 = live ? A.run_first[itc + 1] : r0;
+        for (int r = r0; r < r1; r++) n += RunCursor::sane(A.runs[2 * r], A.runs[2 * r + 1], A.n_samples);
+        rc.runs = A.runs; rc.r = r0 - 1; rc.p = -1; rc.cnt = 0; rc.n_samples = A.n_samples; rc.off = 0;
+        if (n > 0) s0 = (int)rc.next();
+    }
+    if constexpr (SRC == PI_RAW) {
+        // the reference's asserts, found before anything is written: lanes over the samples, then a minimum over the 16 lanes
+        s0 = A.first[itc];
+        const int n_raw = live ? A.first[itc + 1] - s0 : 0;
+        const double* rw = A.samples + (size_t)s0 * 7;
+        tprev = A.t01[(size_t)itc * 2]; t1 = A.t01[(size_t)itc * 2 + 1];
+        int kb = n_raw > 0 ? n_raw : 0, kbad = 0x7fffffff;  // first sample beyond t1; first sample inside (t0, t1] with a negative dt
+        for (int i = c; i < n_raw; i += 16) {
+            const double t = rw[(size_t)i * 7], tp = i ? rw[(size_t)(i - 1) * 7] : tprev;
+            if (!(t <= t1)) kb = min(kb, i);
+            else if (t - tp < 0) kbad = min(kbad, i);
+        }
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) { kb = min(kb, __shfl_xor(kb, m)); kbad = min(kbad, __shfl_xor(kbad, m)); }
+        code = n_raw <= 0 ? SWF_IMUF_EMPTY : kb == 0 ? SWF_IMUF_NO_INNER : kbad < kb ? SWF_IMUF_TIME_ORDER : SWF_IMUF_OK;
+        n = (live && code == SWF_IMUF_OK) ? min(kb + 1, n_raw) + 1 : 0;     // the seed row, then one row per IMUProcess call
+        if (live && c == 0) A.info[itc] = code;
+    }
     const double* __restrict__ smp = A.samples + (size_t)s0 * 7;
-    const double* bb = A.bias + (size_t)itc * 6;
+    const double* bb = SRC == PI_RAW ? A.state + (size_t)itc * 21 + 15 : A.bias + (size_t)itc * 6;
     const double ba[3] = { bb[0], bb[1], bb[2] }, bg[3] = { bb[3], bb[4], bb[5] };
     int nmax = n;
     nmax = max(nmax, __shfl_xor(nmax, 16)); nmax = max(nmax, __shfl_xor(nmax, 32));
@@ -94,21 +166,109 @@ __global__ void __launch_bounds__(64) k_preintegrate(PreintArgs A) {
     for (int i = 0; i < 15; i++) { jc[i] = (i == c) ? 1.0 : 0.0; cc[i] = 0.0; }
     double dp[3] = { 0, 0, 0 }, dq[4] = { 0, 0, 0, 1 }, dv[3] = { 0, 0, 0 }, sum_dt = 0;
     double acc0[3] = { 0, 0, 0 }, gyr0[3] = { 0, 0, 0 };
-    if (n > 0) { acc0[0] = smp[1]; acc0[1] = smp[2]; acc0[2] = smp[3]; gyr0[0] = smp[4]; gyr0[1] = smp[5]; gyr0[2] = smp[6]; }
+    // PI_RAW: the frame's P, R, V (IMUProcess), the previous raw row (the boundary blend) and the frame's cut rows
+    double fP[3] = { 0, 0, 0 }, fR[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, fV[3] = { 0, 0, 0 }, praw[6] = { 0, 0, 0, 0, 0, 0 };
+    double* cutp = nullptr;
+    if constexpr (SRC == PI_RAW) {
+        if (n > 0) {
+            const double* sd = A.seed + (size_t)itc * 6;
+            const double* x = A.state + (size_t)itc * 21;
+            acc0[0] = sd[0]; acc0[1] = sd[1]; acc0[2] = sd[2]; gyr0[0] = sd[3]; gyr0[1] = sd[4]; gyr0[2] = sd[5];
+#pragma unroll
+            for (int k = 0; k < 3; k++) { fP[k] = x[k]; fV[k] = x[12 + k]; }
+#pragma unroll
+            for (int k = 0; k < 9; k++) fR[k] = x[3 + k];
+            // the lever arm comes off (R/swf/swf_imu.cpp:123-125)
+            double rp_[3], wv[3], wx[3], rw_[3];
+            mat3vec(fR, A.pbg, rp_);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { fP[k] -= rp_[k]; wv[k] = A.gyrj_prev[(size_t)itc * 3 + k] - bg[k]; }
+            if (A.flags[itc] & 1) {
+                cross3(wv, A.pbg, wx); mat3vec(fR, wx, rw_);
+#pragma unroll
+                for (int k = 0; k < 3; k++) fV[k] -= rw_[k];
+            }
+            cutp = A.cut + (size_t)(s0 + itc) * 7;
+            if (c == 0) {
+                cutp[0] = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; k++) { cutp[1 + k] = acc0[k]; cutp[4 + k] = gyr0[k]; }
+            }
+        }
+    } else {
+        if (n > 0) { acc0[0] = smp[1]; acc0[1] = smp[2]; acc0[2] = smp[3]; gyr0[0] = smp[4]; gyr0[1] = smp[5]; gyr0[2] = smp[6]; }
+    }
     const double gyri[3] = { gyr0[0], gyr0[1], gyr0[2] };
     double* T = sT[g];
     const int bj = c / 3, b = c - bj * 3;                   // block column / column inside the block of this lane's covariance column
     double nx[7];
+    if constexpr (SRC == PI_CONTIG) {
 #pragma unroll
-    for (int k = 0; k < 7; k++) nx[k] = (n > 1) ? smp[7 + k] : 0.0;
+        for (int k = 0; k < 7; k++) nx[k] = (n > 1) ? smp[7 + k] : 0.0;
+    } else if constexpr (SRC == PI_RUNS) {
+        const double* q = A.samples + (size_t)(n > 1 ? rc.next() : s0) * 7;
+#pragma unroll
+        for (int k = 0; k < 7; k++) nx[k] = (n > 1) ? q[k] : 0.0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 7; k++) nx[k] = (n > 1) ? smp[k] : 0.0;         // raw row 0 is effective sample 1
+    }
     for (int s = 1; s < nmax; s++) {
         const bool act = s < n;
         double cur[7];
 #pragma unroll
         for (int k = 0; k < 7; k++) cur[k] = nx[k];
         if (s + 1 < n) {
+            const double* q = SRC == PI_CONTIG ? smp + (s + 1) * 7 : SRC == PI_RAW ? smp + (size_t)s * 7 : A.samples + (size_t)rc.next() * 7;
 #pragma unroll
-            for (int k = 0; k < 7; k++) nx[k] = smp[(s + 1) * 7 + k];       // prefetch the next sample under this step's arithmetic
+            for (int k = 0; k < 7; k++) nx[k] = q[k];                       // prefetch the next sample under this step's arithmetic
+        }
+        if constexpr (SRC == PI_RAW) {
+            if (act) {
+                // the cut (R/swf/swf_imu.cpp:134-166): a sample up to t1 as it is, the one beyond blended onto t1 with the raw row before it
+                const double t = cur[0];
+                double e[7];
+                if (t <= t1) {
+                    e[0] = t - tprev; tprev = t;
+#pragma unroll
+                    for (int k = 1; k < 7; k++) e[k] = cur[k];
+                } else {
+                    const double dt_1 = t1 - tprev, dt_2 = t - t1;
+                    const double w1 = dt_2 / (dt_1 + dt_2), w2 = dt_1 / (dt_1 + dt_2);
+                    e[0] = dt_1; tprev = t1;
+#pragma unroll
+                    for (int k = 1; k < 7; k++) e[k] = w1 * praw[k - 1] + w2 * cur[k];
+                }
+#pragma unroll
+                for (int k = 0; k < 6; k++) praw[k] = cur[1 + k];
+#pragma unroll
+                for (int k = 0; k < 7; k++) cur[k] = pinned(e[k]);
+                if (c == 0) {
+#pragma unroll
+                    for (int k = 0; k < 7; k++) cutp[(size_t)s * 7 + k] = cur[k];
+                }
+                // IMUProcess (:202-208).  M(theta) is Eigen's toRotationMatrix of the UNNORMALISED quaternion (1, theta / 2) that
+                // Utility::deltaQ returns: R does not stay orthonormal, as in the reference
+                const double fdt = cur[0];
+                double a0[3], a1[3], u0[3], u1[3], hq[4], M[9], Rn[9];
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    a0[k] = acc0[k] - ba[k]; a1[k] = cur[1 + k] - ba[k];
+                    hq[k] = (0.5 * (gyr0[k] + cur[4 + k]) - bg[k]) * fdt / 2.0;
+                }
+                hq[3] = 1.0;
+                mat3vec(fR, a0, u0);
+                q2R(hq, M); mat3mul(fR, M, Rn);
+                mat3vec(Rn, a1, u1);
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const double un = 0.5 * ((u0[k] - A.gw[k]) + (u1[k] - A.gw[k]));
+                    fP[k] += fdt * fV[k] + 0.5 * fdt * fdt * un;
+                    fV[k] += fdt * un;
+                }
+#pragma unroll
+                for (int k = 0; k < 9; k++) fR[k] = Rn[k];
+            }
         }
         if (act) {
             const double dt = cur[0];
@@ -188,7 +348,29 @@ __global__ void __launch_bounds__(64) k_preintegrate(PreintArgs A) {
         }
     }
     double* out = A.pre + (size_t)itc * SWF_PRE_DOUBLES;
-    if (live && c == 0) {
+    const bool wr = live && (SRC != PI_RAW || n > 0);       // a failed frame writes its info and nothing else
+    if constexpr (SRC == PI_RAW) {
+        if (wr) {
+            // the lever arm goes back on, with the final R and the last effective gyr (R/swf/swf_imu.cpp:172-174)
+            double rp_[3], wv[3], wx[3], rw_[3];
+            mat3vec(fR, A.pbg, rp_);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { fP[k] += rp_[k]; wv[k] = gyr0[k] - bg[k]; }
+            if (A.flags[itc] & 1) {
+                cross3(wv, A.pbg, wx); mat3vec(fR, wx, rw_);
+#pragma unroll
+                for (int k = 0; k < 3; k++) fV[k] += rw_[k];
+            }
+            if (c == 0) {
+                double* pr = A.pred + (size_t)itc * 15;
+#pragma unroll
+                for (int k = 0; k < 3; k++) { pr[k] = fP[k]; pr[12 + k] = fV[k]; }
+#pragma unroll
+                for (int k = 0; k < 9; k++) pr[3 + k] = fR[k];
+            }
+        }
+    }
+    if (wr && c == 0) {
         for (int k = 0; k < 3; k++) {
             out[SWF_PRE_DP + k] = dp[k]; out[SWF_PRE_DV + k] = dv[k]; out[SWF_PRE_LBA + k] = ba[k]; out[SWF_PRE_LBG + k] = bg[k];
             out[SWF_PRE_GYRI + k] = gyri[k]; out[SWF_PRE_GYRJ + k] = gyr0[k];
@@ -196,7 +378,7 @@ __global__ void __launch_bounds__(64) k_preintegrate(PreintArgs A) {
         for (int k = 0; k < 4; k++) out[SWF_PRE_DQ + k] = dq[k];
         out[SWF_PRE_SUMDT] = sum_dt;
     }
-    if (live && c >= 9 && c < 15) {                         // the five 3x3 bias-Jacobian blocks: columns 9-11 (ba) and 12-14 (bg)
+    if (wr && c >= 9 && c < 15) {                        // the five 3x3 bias-Jacobian blocks: columns 9-11 (ba) and 12-14 (bg)
         const int cb = c >= 12 ? c - 12 : c - 9;
 #pragma unroll
         for (int a = 0; a < 3; a++) {
@@ -250,7 +432,7 @@ __global__ void __launch_bounds__(64) k_preintegrate(PreintArgs A) {
     PI_BACK_ROW(6) PI_BACK_ROW(5) PI_BACK_ROW(4) PI_BACK_ROW(3) PI_BACK_ROW(2) PI_BACK_ROW(1) PI_BACK_ROW(0)
 #undef PI_T
 #undef PI_BACK_ROW
-    if (live && c < 15) {
+    if (wr && c < 15) {
 #pragma unroll
         for (int i = 0; i < 15; i++) out[SWF_PRE_SQRTINFO + i * 15 + c] = ok ? u[i] : 0.0;
     }
@@ -269,7 +451,7 @@ extern "C" int swf_preintegrate_batch(const double* samples, const int32_t* firs
     A.n_int = n_intervals;
     if (on_device) {
         A.samples = samples; A.first = first; A.bias = bias; A.pre = pre;
-        hipLaunchKernelGGL(k_preintegrate, dim3((n_intervals + PI_GROUPS - 1) / PI_GROUPS), dim3(64), 0, st, A);
+        hipLaunchKernelGGL(k_preintegrate<PI_CONTIG>, dim3((n_intervals + PI_GROUPS - 1) / PI_GROUPS), dim3(64), 0, st, A);
         PI_HIPCHK(hipGetLastError());
         return SWF_OK;
     }
@@ -289,7 +471,7 @@ extern "C" int swf_preintegrate_batch(const double* samples, const int32_t* firs
     PI_TRY(hipMemcpyAsync(d_b, bias, (size_t)n_intervals * 6 * sizeof(double), hipMemcpyHostToDevice, st));
     PI_TRY(hipMemcpyAsync(d_f, rel.data(), rel.size() * sizeof(int), hipMemcpyHostToDevice, st));
     A.samples = d_s; A.first = d_f; A.bias = d_b; A.pre = d_o;
-    hipLaunchKernelGGL(k_preintegrate, dim3((n_intervals + PI_GROUPS - 1) / PI_GROUPS), dim3(64), 0, st, A);
+    hipLaunchKernelGGL(k_preintegrate<PI_CONTIG>, dim3((n_intervals + PI_GROUPS - 1) / PI_GROUPS), dim3(64), 0, st, A);
     PI_TRY(hipGetLastError());
     PI_TRY(hipMemcpyAsync(pre, d_o, (size_t)n_intervals * SWF_PRE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, st));
     PI_TRY(hipStreamSynchronize(st));
@@ -297,6 +479,147 @@ extern "C" int swf_preintegrate_batch(const double* samples, const int32_t* firs
     cleanup();
     return SWF_OK;
 }
+
+namespace {
+// device buffers of one host-memory call, freed on every way out
+struct PiBufs {
+    std::vector<void*> p;
+    ~PiBufs() { for (void* q : p) (void)hipFree(q); }
+    hipError_t up(void** d, const void* h, size_t bytes, hipStream_t st) {
+        hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 8));
+        if (e != hipSuccess) return e;
+        p.push_back(*d);
+        return (h && bytes) ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+    }
+};
+#define PI_TRYB(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return pi_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+// what the kernel's first pass finds, on host memory: the SWF_IMUF_* code of one frame and its number of cut rows
+int imuf_classify(const double* raw, int n_raw, double t0, double t1, int* rows) {
+    *rows = 0;
+    if (n_raw <= 0) return SWF_IMUF_EMPTY;
+    if (!(raw[0] <= t1)) return SWF_IMUF_NO_INNER;
+    double tp = t0;
+    int i = 0;
+    for (; i < n_raw && raw[(size_t)i * 7] <= t1; i++) {
+        if (raw[(size_t)i * 7] - tp < 0) return SWF_IMUF_TIME_ORDER;
+        tp = raw[(size_t)i * 7];
+    }
+    *rows = std::min(i + 1, n_raw) + 1;
+    return SWF_IMUF_OK;
+}
+}  // namespace
+
+extern "C" int swf_preintegrate_runs_batch(const double* samples, int32_t n_samples, const int32_t* runs, const int32_t* run_first,
+                                           int32_t n_intervals, const double* bias, const double noise[4], double* pre,
+                                           int32_t on_device, void* stream) {
+    if (!samples || !runs || !run_first || !bias || !noise || !pre || n_intervals < 0 || n_samples < 0)
+        return pi_fail(SWF_E_INVALID, "swf_preintegrate_runs_batch: null argument");
+    if (n_intervals == 0) return SWF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    PreintArgs A{};
+    A.acc_n2 = noise[0] * noise[0]; A.gyr_n2 = noise[1] * noise[1]; A.acc_w2 = noise[2] * noise[2]; A.gyr_w2 = noise[3] * noise[3];
+    A.n_int = n_intervals; A.n_samples = n_samples;
+    const dim3 grid((n_intervals + PI_GROUPS - 1) / PI_GROUPS);
+    if (on_device) {
+        A.samples = samples; A.runs = runs; A.run_first = run_first; A.bias = bias; A.pre = pre;
+        hipLaunchKernelGGL(k_preintegrate<PI_RUNS>, grid, dim3(64), 0, st, A);
+        PI_HIPCHK(hipGetLastError());
+        return SWF_OK;
+    }
+    if (run_first[0] < 0) return pi_fail(SWF_E_INVALID, "swf_preintegrate_runs_batch: run offsets must be non-negative");
+    for (int i = 0; i < n_intervals; i++)
+        if (run_first[i + 1] < run_first[i]) return pi_fail(SWF_E_INVALID, "swf_preintegrate_runs_batch: run offsets must be non-decreasing");
+    const int r0 = run_first[0], nr = run_first[n_intervals] - r0;
+    for (int r = r0; r < r0 + nr; r++)
+        if (runs[2 * r] < 0 || runs[2 * r + 1] < 0 || (int64_t)runs[2 * r] + runs[2 * r + 1] > n_samples)
+            return pi_fail(SWF_E_INVALID, "swf_preintegrate_runs_batch: a run leaves the sample array");
+    std::vector<int32_t> rel(run_first, run_first + n_intervals + 1);
+    for (auto& v : rel) v -= r0;
+    PiBufs B;
+    void *d_s, *d_r, *d_f, *d_b, *d_o;
+    PI_TRYB(B.up(&d_s, samples, (size_t)n_samples * 7 * sizeof(double), st));
+    PI_TRYB(B.up(&d_r, runs + (size_t)2 * r0, (size_t)nr * 2 * sizeof(int32_t), st));
+    PI_TRYB(B.up(&d_f, rel.data(), rel.size() * sizeof(int32_t), st));
+    PI_TRYB(B.up(&d_b, bias, (size_t)n_intervals * 6 * sizeof(double), st));
+    PI_TRYB(B.up(&d_o, nullptr, (size_t)n_intervals * SWF_PRE_DOUBLES * sizeof(double), st));
+    A.samples = (const double*)d_s; A.runs = (const int*)d_r; A.run_first = (const int*)d_f; A.bias = (const double*)d_b; A.pre = (double*)d_o;
+    hipLaunchKernelGGL(k_preintegrate<PI_RUNS>, grid, dim3(64), 0, st, A);
+    PI_TRYB(hipGetLastError());
+    PI_TRYB(hipMemcpyAsync(pre, d_o, (size_t)n_intervals * SWF_PRE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, st));
+    PI_TRYB(hipStreamSynchronize(st));
+    return SWF_OK;
+}
+
+extern "C" int swf_imu_frame_batch(const double* raw, const int32_t* first, int32_t n_frames, const double* t01, const double* seed,
+                                   const double* state, const double* gyrj_prev, const int32_t* flags, const double pbg[3],
+                                   const double g_w[3], const double noise[4], double* cut, double* pre, double* pred, int32_t* info,
+                                   int32_t on_device, void* stream) {
+    if (!raw || !first || !t01 || !seed || !state || !gyrj_prev || !flags || !pbg || !g_w || !noise || !cut || !pre || !pred || !info || n_frames < 0)
+        return pi_fail(SWF_E_INVALID, "swf_imu_frame_batch: null argument");
+    if (n_frames == 0) return SWF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    PreintArgs A{};
+    A.acc_n2 = noise[0] * noise[0]; A.gyr_n2 = noise[1] * noise[1]; A.acc_w2 = noise[2] * noise[2]; A.gyr_w2 = noise[3] * noise[3];
+    A.n_int = n_frames;
+    for (int k = 0; k < 3; k++) { A.pbg[k] = pbg[k]; A.gw[k] = g_w[k]; }
+    const dim3 grid((n_frames + PI_GROUPS - 1) / PI_GROUPS);
+    if (on_device) {
+        A.samples = raw; A.first = first; A.t01 = t01; A.seed = seed; A.state = state; A.gyrj_prev = gyrj_prev; A.flags = flags;
+        A.cut = cut; A.pre = pre; A.pred = pred; A.info = info;
+        hipLaunchKernelGGL(k_preintegrate<PI_RAW>, grid, dim3(64), 0, st, A);
+        PI_HIPCHK(hipGetLastError());
+        return SWF_OK;
+    }
+    for (int i = 0; i < n_frames; i++)
+        if (first[i + 1] < first[i]) return pi_fail(SWF_E_INVALID, "swf_imu_frame_batch: sample offsets must be non-decreasing");
+    // the per-frame failures, before the device is touched
+    std::vector<int> rows(n_frames);
+    int n_ok = 0;
+    for (int i = 0; i < n_frames; i++) {
+        info[i] = imuf_classify(raw + (size_t)first[i] * 7, first[i + 1] - first[i], t01[2 * i], t01[2 * i + 1], &rows[i]);
+        n_ok += info[i] == SWF_IMUF_OK;
+    }
+    if (!n_ok) return SWF_OK;
+    const size_t ns = (size_t)(first[n_frames] - first[0]), nf = (size_t)n_frames;
+    std::vector<int32_t> rel(first, first + n_frames + 1);
+    for (auto& v : rel) v -= first[0];
+    PiBufs B;
+    void *d_s, *d_f, *d_t, *d_sd, *d_x, *d_g, *d_fl, *d_c, *d_o, *d_p, *d_i;
+    PI_TRYB(B.up(&d_s, raw + (size_t)first[0] * 7, ns * 7 * sizeof(double), st));
+    PI_TRYB(B.up(&d_f, rel.data(), rel.size() * sizeof(int32_t), st));
+    PI_TRYB(B.up(&d_t, t01, nf * 2 * sizeof(double), st));
+    PI_TRYB(B.up(&d_sd, seed, nf * 6 * sizeof(double), st));
+    PI_TRYB(B.up(&d_x, state, nf * 21 * sizeof(double), st));
+    PI_TRYB(B.up(&d_g, gyrj_prev, nf * 3 * sizeof(double), st));
+    PI_TRYB(B.up(&d_fl, flags, nf * sizeof(int32_t), st));
+    PI_TRYB(B.up(&d_c, nullptr, (ns + nf) * 7 * sizeof(double), st));
+    PI_TRYB(B.up(&d_o, nullptr, nf * SWF_PRE_DOUBLES * sizeof(double), st));
+    PI_TRYB(B.up(&d_p, nullptr, nf * 15 * sizeof(double), st));
+    PI_TRYB(B.up(&d_i, nullptr, nf * sizeof(int32_t), st));
+    A.samples = (const double*)d_s; A.first = (const int*)d_f; A.t01 = (const double*)d_t; A.seed = (const double*)d_sd;
+    A.state = (const double*)d_x; A.gyrj_prev = (const double*)d_g; A.flags = (const int*)d_fl;
+    A.cut = (double*)d_c; A.pre = (double*)d_o; A.pred = (double*)d_p; A.info = (int*)d_i;
+    hipLaunchKernelGGL(k_preintegrate<PI_RAW>, grid, dim3(64), 0, st, A);
+    PI_TRYB(hipGetLastError());
+    // a failed frame leaves the caller's cut / pre / pred as they are: the results pass through staging arrays
+    std::vector<double> h_c((ns + nf) * 7), h_o(nf * SWF_PRE_DOUBLES), h_p(nf * 15);
+    std::vector<int32_t> h_i(nf);
+    PI_TRYB(hipMemcpyAsync(h_c.data(), d_c, h_c.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    PI_TRYB(hipMemcpyAsync(h_o.data(), d_o, h_o.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    PI_TRYB(hipMemcpyAsync(h_p.data(), d_p, h_p.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    PI_TRYB(hipMemcpyAsync(h_i.data(), d_i, h_i.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    PI_TRYB(hipStreamSynchronize(st));
+    for (int i = 0; i < n_frames; i++) {
+        if (h_i[i] != info[i]) return pi_fail(SWF_E_STATE, "swf_imu_frame_batch: the device classified a frame differently from the host");
+        if (info[i] != SWF_IMUF_OK) continue;
+        std::copy(h_c.begin() + (size_t)(rel[i] + i) * 7, h_c.begin() + (size_t)(rel[i] + i + rows[i]) * 7, cut + (size_t)(first[i] + i) * 7);
+        std::copy(h_o.begin() + (size_t)i * SWF_PRE_DOUBLES, h_o.begin() + (size_t)(i + 1) * SWF_PRE_DOUBLES, pre + (size_t)i * SWF_PRE_DOUBLES);
+        std::copy(h_p.begin() + (size_t)i * 15, h_p.begin() + (size_t)(i + 1) * 15, pred + (size_t)i * 15);
+    }
+    return SWF_OK;
+}
+#undef PI_TRYB
 
 // =====================================================================================================================
 // (2) two-view landmark triangulation: FeatureManager::triangulate, the branch every feature with >= 2 observations takes

@@ -62,6 +62,7 @@ EXPORTED = [
     "swf_phase_screen_batch",
     "swf_gnss_epoch_solve_batch",
     "swf_dd_select_batch", "swf_batch_select_ambiguity_pairs", "swf_batch_ambiguity_search_selected", "swf_batch_get_ambiguity_pairs",
+    "swf_imu_frame_batch", "swf_preintegrate_runs_batch",
 ]
 
 
@@ -865,6 +866,58 @@ def preintegrate_batch(samples, biases, noise):
     _chk(lib().swf_preintegrate_batch(flat.ctypes.data_as(_pd), first.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int32(n),
                                       b.ctypes.data_as(_pd), nz, out.ctypes.data_as(_pd), C.c_int32(0), None), "preintegrate_batch")
     return out
+
+
+def preintegrate_runs_batch(samples, runs, biases, noise):
+    """swf_preintegrate_batch over a gather list (swf_preintegrate_runs_batch): samples [N][7] is one resident array, runs a list, per
+    interval, of (offset, count) pairs into it.  The first row of an interval's first non-empty run seeds acc_0 / gyr_0, every
+    further row is a push_back.  Returns the [n][PRE_DOUBLES] records, bit-identical to preintegrate_batch on the concatenated rows."""
+    n = len(runs)
+    s = np.ascontiguousarray(np.asarray(samples, np.float64).reshape(-1, 7))
+    run_first = np.zeros(n + 1, np.int32)
+    for i, r in enumerate(runs):
+        run_first[i + 1] = run_first[i] + np.asarray(r, np.int64).reshape(-1, 2).shape[0]
+    rr = [np.asarray(r, np.int32).reshape(-1, 2) for r in runs]
+    flat = np.ascontiguousarray(np.concatenate(rr)) if n and run_first[n] else np.zeros((1, 2), np.int32)
+    b = np.ascontiguousarray(np.asarray(biases, np.float64).reshape(n, 6))
+    nz = (C.c_double * 4)(*[float(v) for v in noise])
+    out = np.zeros((n, 293))
+    pi = C.POINTER(C.c_int32)
+    sp = s if s.size else np.zeros((1, 7))
+    _chk(lib().swf_preintegrate_runs_batch(sp.ctypes.data_as(_pd), C.c_int32(s.shape[0]), flat.ctypes.data_as(pi), run_first.ctypes.data_as(pi),
+                                           C.c_int32(n), b.ctypes.data_as(_pd), nz, out.ctypes.data_as(_pd), C.c_int32(0), None),
+         "preintegrate_runs_batch")
+    return out
+
+
+IMUF_OK, IMUF_EMPTY, IMUF_NO_INNER, IMUF_TIME_ORDER = 0, 1, 2, 3
+
+
+def imu_frame_batch(raw, t01, seed, state, gyrj_prev, flags, pbg, g_w, noise, fill=0.0):
+    """SWFOptimization::ImuIntegrate + IMUProcess (R/swf/swf_imu.cpp:117-213) for a batch of frames on the device
+    (swf_imu_frame_batch).  raw: list of [n_f][7] arrays (t, acc, gyr: what GetImuInterval returns); t01 [n][2]; seed [n][6] (acc_0,
+    gyr_0 on entry); state [n][21] (P, R row-major, V, ba, bg); gyrj_prev [n][3]; flags [n] (bit 0: velocity lever arm); pbg, g_w [3];
+    noise = (ACC_N, GYR_N, ACC_W, GYR_W).  Returns dict(cut, first, pre, pred, info): cut [sum n_f + n][7] in preintegrate_batch's
+    layout, frame f owning rows first[f] + f .. first[f + 1] + f; a frame whose info is not IMUF_OK leaves its rows at `fill`."""
+    n = len(raw)
+    rr = [np.asarray(r, np.float64).reshape(-1, 7) for r in raw]
+    first = np.zeros(n + 1, np.int32)
+    for i, r in enumerate(rr):
+        first[i + 1] = first[i] + r.shape[0]
+    flat = np.ascontiguousarray(np.concatenate(rr)) if n and first[n] else np.zeros((1, 7))
+    a = [np.ascontiguousarray(np.asarray(v, np.float64).reshape(n, k)) for v, k in ((t01, 2), (seed, 6), (state, 21), (gyrj_prev, 3))]
+    fl = np.ascontiguousarray(np.asarray(flags, np.int32).reshape(n))
+    v3 = lambda v: (C.c_double * 3)(*[float(x) for x in np.asarray(v, np.float64).reshape(3)])
+    nz = (C.c_double * 4)(*[float(v) for v in noise])
+    cut = np.full((int(first[n]) + n, 7), float(fill)); pre = np.full((n, 293), float(fill)); pred = np.full((n, 15), float(fill))
+    info = np.full(n, -1, np.int32)
+    pi = C.POINTER(C.c_int32)
+    if n:
+        _chk(lib().swf_imu_frame_batch(flat.ctypes.data_as(_pd), first.ctypes.data_as(pi), C.c_int32(n), a[0].ctypes.data_as(_pd),
+                                       a[1].ctypes.data_as(_pd), a[2].ctypes.data_as(_pd), a[3].ctypes.data_as(_pd), fl.ctypes.data_as(pi),
+                                       v3(pbg), v3(g_w), nz, cut.ctypes.data_as(_pd), pre.ctypes.data_as(_pd), pred.ctypes.data_as(_pd),
+                                       info.ctypes.data_as(pi), C.c_int32(0), None), "imu_frame_batch")
+    return dict(cut=cut, first=first, pre=pre, pred=pred, info=info)
 
 
 def triangulate_batch(Ps, Rs, tic, ric, pbg, start_frame, pt0, pt1, init_depth=5.0):
