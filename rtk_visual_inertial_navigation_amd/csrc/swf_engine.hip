@@ -267,6 +267,7 @@ struct swf_batch {
     int ls_qpb = 1, ls_var = 0, ls_kms = 8; bool ls_folded = false, s_direct = false;     // k_lm_schur launch shape, fixed at creation (the pair lists depend on it)
     bool full_final = false;              // SWF_FULL_FINAL_ELIM=1: the solve's final linearisation runs the complete group-0 elimination, as every other one does (parity: bit-identical to the gradient-only pass)
     bool no_clq_pack = false;             // SWF_NO_CLIQUE_PACK=1: class 0 as one wavefront per clique (k_clique_elim<48,32,1,0>) instead of two cliques per wavefront (k_clique_pack) (parity, A/B: bit-identical)
+    bool no_clq_mfma = false;             // SWF_NO_CLIQUE_MFMA=1: class 1 of the batch path as k_clique_elim<32,48,9,1> (VALU products) instead of k_clique_mm (matrix cores) (parity, A/B: bit-identical)
     int clp_rows = 1, clp_ld = 3;         // k_clique_pack: rows and leading dimension of its LDS Jacobians (the largest class-0 clique of the batch)
     int ls_gqpb = 4;                      // landmark parts per workgroup of the gradient-only landmark pass (it has no ring to fill: chosen for occupancy, not by ls_qpb)
     int timing = 0;                       // bitmask of SWF_K_* brackets
@@ -308,6 +309,7 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
     b->no_decide_fuse = getenv("SWF_NO_DECIDE_FUSE") != nullptr;
     b->full_final = getenv("SWF_FULL_FINAL_ELIM") != nullptr;
     b->no_clq_pack = getenv("SWF_NO_CLIQUE_PACK") != nullptr;
+    b->no_clq_mfma = getenv("SWF_NO_CLIQUE_MFMA") != nullptr;
     // what the launcher reads of the plan
     b->max_tiles = B.max_tiles; b->max_prior_dim = B.max_prior_dim; b->max_red = B.max_red; b->min_red = B.min_red;
     b->rr_nmax = B.rr_nmax; b->rr4_has15 = B.rr4_has15; b->rr4_has16 = B.rr4_has16; b->n_pch_split = B.n_pch_split;
@@ -755,7 +757,8 @@ struct Launcher {
             if (D.n_clc[1]) {
                 Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(1));
                 if (grad) hipLaunchKernelGGL((k_clique_elim<32, 48, 9, 1, true>), dim3(D.n_clc[1]), dim3(64), 0, cstream(1), D, O);
-                else hipLaunchKernelGGL((k_clique_elim<32, 48, 9, 1>), dim3(D.n_clc[1]), dim3(64), 0, cstream(1), D, O);
+                else if (b->no_clq_mfma) hipLaunchKernelGGL((k_clique_elim<32, 48, 9, 1>), dim3(D.n_clc[1]), dim3(64), 0, cstream(1), D, O);
+                else hipLaunchKernelGGL((k_clique_mm<32, 48, 9>), dim3(D.n_clc[1]), dim3(64), 0, cstream(1), D, O);      // batch path: J^T J and the C update on the matrix cores, same bits
             }
             if (D.n_clc[0]) {
                 Bracket t(*this, SWF_K_CLIQUE_ELIM, cstream(0));
@@ -1833,6 +1836,23 @@ extern "C" int swf_debug_plan_check(const swf_flat_window* const* windows, int32
     }
     rc = plan_validate(B, err);
     return rc == SWF_OK ? SWF_OK : fail(rc, err);
+}
+
+// One v_mfma_f64_16x16x4_f64 on the given operands (host pointers, row-major: A 16 x 4, B 4 x 16, C and D 16 x 16): what k_clique_mm
+// rests on is the order in which the instruction accumulates its four k-slots (tests/test_clique_mfma_gpu.py).
+extern "C" int swf_debug_mfma_f64(const double* A, const double* Bm, const double* C, double* D) {
+    if (!A || !Bm || !C || !D) return fail(SWF_E_INVALID, "swf_debug_mfma_f64: bad arguments");
+    double* dv = nullptr;
+    if (hipMalloc(&dv, (64 + 64 + 256 + 256) * sizeof(double)) != hipSuccess) return fail(SWF_E_NODEVICE, "swf_debug_mfma_f64: allocation failed");
+    bool ok = hipMemcpy(dv, A, 64 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+        && hipMemcpy(dv + 64, Bm, 64 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+        && hipMemcpy(dv + 128, C, 256 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_debug_mfma_f64, dim3(1), dim3(64), 0, 0, dv, dv + 64, dv + 128, dv + 384);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(D, dv + 384, 256 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(dv);
+    return ok ? SWF_OK : fail(SWF_E_NODEVICE, "swf_debug_mfma_f64: the device run failed");
 }
 
 #ifdef SWF_PROFILE_CHOL

@@ -1293,6 +1293,9 @@ __global__ void __launch_bounds__(256) k_clique_elim4(DevBatch B, DevOpt O) { d_
 template <bool GRAD = false>
 __global__ void __launch_bounds__(256) k_clique_tall(DevBatch B, DevOpt O) { d_clique_elim<CLQ_TALLR, 64, 9, 4, 8, 4, 4, GRAD>(B, O, (int)blockIdx.x); }
 
+// class 1 on the batch path: the same elimination with its products on the matrix cores (k_clique_mm)
+#include "swf_clique_mm.h"
+
 // Class 0 on the batch path, PACKED: two cliques per wavefront.  A class-0 clique has d_e <= 1 and d <= 32 columns (the bench's receiver
 // clocks: 20 rows x 17 columns), so one wavefront per clique leaves two thirds of its lanes idle and — with LDS declared for the class
 // envelope — 12 cliques on a CU.  Here lanes 0-31 take clique 2i and lanes 32-63 clique 2i + 1 of clc_rec[0], "lane" below is the lane

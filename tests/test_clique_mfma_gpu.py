@@ -1,0 +1,210 @@
+"""Class-1 cliques of the batch path (speed-bias blocks with their IMU factors) are eliminated by k_clique_mm: J^T J and the C update
+as v_mfma_f64_16x16x4_f64 tiles.  SWF_NO_CLIQUE_MFMA=1 keeps k_clique_elim<32,48,9,1>, whose sums are k-ascending fma chains on the VALU;
+the two must give the same BYTES.
+
+Step 0 is the property that makes this possible: per output element the instruction computes
+    fma(a[s3], b[s3], fma(a[s2], b[s2], fma(a[s1], b[s1], fma(a[s0], b[s0], c))))
+for ONE fixed order (s0, s1, s2, s3) of its four k-slots.  test_mfma_f64_is_a_slot_ordered_fma_chain runs one MFMA through
+swf_debug_mfma_f64 on operands whose exponents spread over 2^-40 .. 2^40 and compares its bytes with all 24 orders, each computed
+exactly on the host (rational arithmetic, one rounding per fma).  Exactly one order may match, and it is the ascending one that
+k_clique_mm's slot table (CMM_SLOT_ROW in csrc/swf_clique_mm.h) assumes.
+
+The knob is read when a batch is created, so each side of a comparison is a fresh child process (this file run as a script), after
+tests/test_clique_pack_gpu.py: states, every summary field, the whole trace, and export_reduced / export_vectors of an
+ASSEMBLE_ELIMINATE_ONLY solve.  Both children set SWF_NO_LAT_FUSE=1, so that a handful of windows takes the batch path and class 1 exists.
+
+Shapes of the class-1 cliques in the cases (rows x columns, d_e = 9):
+  two IMU factors            30 x 45    (k-steps: 8, the last with two zero rows)
+  one IMU factor             15 x 30    (the last speed-bias block of an even K: 4 k-steps, one zero row, two tile columns)
+  one pose held constant     30 x 39 and 15 x 24
+  Doppler, S = 2             32 x 46 and 17 x 31   (two Doppler rows and the clock-drift column join the clique)
+32 rows is the class's row limit.  46 columns is the widest class-1 clique synth can produce (S = 3 already has 33 rows and leaves the
+class), so columns 46 and 47 of the 32 x 48 envelope are never occupied by a test: they are zero columns of the third tile either way."""
+import ctypes
+import itertools
+import os
+import subprocess
+import sys
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KNOB = "SWF_NO_CLIQUE_MFMA"
+SUMMARY_FIELDS = ("initial_cost", "final_cost", "minimizer_time_in_seconds", "num_successful_steps", "num_unsuccessful_steps",
+                  "num_iterations", "termination", "reduced_dim", "tail_dim")
+TRACE_FIELDS = ("cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease", "trust_region_radius",
+                "model_cost_change", "step_is_successful", "step_is_valid")
+
+
+# ------------------------------------------------------------------------------------------------------------------- step 0
+def _fma(a, b, c):
+    """fma(a, b, c) of three doubles, exactly: the rational a b + c rounded once, to nearest even (float(Fraction))."""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _spread(rng, shape):
+    """doubles with full random mantissas, random signs and exponents uniform over 2^-40 .. 2^40"""
+    return np.ldexp(rng.uniform(1.0, 2.0, shape) * rng.choice([-1.0, 1.0], shape), rng.integers(-40, 41, shape))
+
+
+@pytest.mark.gpu
+def test_mfma_f64_is_a_slot_ordered_fma_chain():
+    from rtk_visual_inertial_navigation_amd import solver
+    lib = solver.lib()
+    rng = np.random.Generator(np.random.PCG64(20241))
+    A, B, Cm = _spread(rng, (16, 4)), _spread(rng, (4, 16)), _spread(rng, (16, 16))
+    D = np.zeros((16, 16))
+    ptr = lambda x: x.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    rc = lib.swf_debug_mfma_f64(ptr(A), ptr(B), ptr(Cm), ptr(D))
+    assert rc == 0, lib.swf_last_error().decode()
+    orders = list(itertools.permutations(range(4)))
+    host = {}
+    for o in orders:
+        H = np.empty((16, 16))
+        for i in range(16):
+            for j in range(16):
+                m = Cm[i, j]
+                for s in o:
+                    m = _fma(A[i, s], B[s, j], m)
+                H[i, j] = m
+        host[o] = H
+    # the operands tell the orders apart: no two of the 24 host results are the same bytes
+    assert len({H.tobytes() for H in host.values()}) == 24
+    match = [o for o in orders if host[o].tobytes() == D.tobytes()]
+    same = {o: int((host[o].view(np.uint64) == D.view(np.uint64)).sum()) for o in orders}
+    print("orders whose bytes the MFMA reproduces:", match)
+    print("elements (of 256) equal per order:", same)
+    assert match == [(0, 1, 2, 3)], (match, same)
+
+
+# ---------------------------------------------------------------------------------------------------------------- child side
+def _with_constant(win, pose):
+    """The same window with one pose block held constant, the elimination ordering re-issued."""
+    from rtk_visual_inertial_navigation_amd.ordering import my_ordering
+    w = win.copy()
+    roles = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in w.meta["roles"].items()}
+    is_const = w.a["is_const"].copy()
+    is_const[pose] = 1
+    o_b, o_g, nt = my_ordering(roles, is_const)
+    w.a["is_const"] = np.ascontiguousarray(is_const, np.uint8)
+    w.a["order_block"], w.a["order_group"], w.n_tail = o_b, o_g, int(nt)
+    return w
+
+
+def _three(synth):
+    return [synth.make_window(3, K=6, F=30, S=5, seed=1010 + i) for i in range(3)]
+
+
+def _case(name):
+    """-> (windows, options)"""
+    from rtk_visual_inertial_navigation_amd import synth
+    from rtk_visual_inertial_navigation_amd.flat import default_options
+    if name == "dogleg":
+        return _three(synth), default_options()
+    if name == "lm":
+        return _three(synth), default_options(strategy=1)
+    if name == "constant_pose":
+        return [synth.make_window(3, K=6, F=30, S=5, seed=1020), _with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1021), pose=2),
+                _with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1022), pose=5)], default_options()
+    if name == "even_odd_k":
+        # K = 6: the last speed-bias clique holds one IMU factor (15 rows); K = 7: every one holds two
+        return [synth.make_window(3, K=6, F=30, S=5, seed=1030), synth.make_window(3, K=7, F=30, S=5, seed=1031),
+                synth.make_window(3, K=5, F=30, S=5, seed=1032)], default_options()
+    if name == "early_stop":
+        still = synth.make_window(2, seed=706, perturb=False)
+        return ([synth.make_window(config_id=3, F=103, seed=701), still, synth.make_window(3, seed=707), still.copy(),
+                 synth.make_window(config_id=3, F=205, seed=702)], default_options(max_num_iterations=20))
+    if name == "nan_pose":
+        ws = _three(synth)
+        ws[1].a["pose"].reshape(-1, 7)[1, 0] = np.nan
+        return ws, default_options()
+    if name == "envelope":
+        # Doppler with S = 2: 30 + 2 rows, 45 + 1 columns (the clock drift) -- see the module docstring
+        return [synth.make_window(3, K=6, F=30, S=2, seed=1040, doppler=True), synth.make_window(3, K=6, F=30, S=5, seed=1041),
+                synth.with_spp_and_fixed(synth.make_window(3, K=6, F=30, S=5, seed=1042), seed=12, n_fix=2)], default_options()
+    raise KeyError(name)
+
+
+def _child(name, path):
+    for p in (ROOT, os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    from rtk_visual_inertial_navigation_amd import solver
+    from rtk_visual_inertial_navigation_amd.flat import default_options
+    out = {}
+    # the linearisation at the uploaded state alone: the reduced system and the local vectors the eliminations wrote
+    if name != "nan_pose":
+        ws, opt = _case(name)
+        bs = solver.BatchSolver(ws)
+        bs.solve(default_options(step_mode=1), download=False)
+        for i in range(len(ws)):
+            S, rhs, _ = bs.export_reduced(i)
+            g, d, _ = bs.export_vectors(i)
+            out["w%d_elim_S" % i] = S; out["w%d_elim_rhs" % i] = rhs; out["w%d_elim_g" % i] = g; out["w%d_elim_diag" % i] = d
+        bs.close()
+    ws, opt = _case(name)
+    bs = solver.BatchSolver(ws)
+    sms = bs.solve(opt)
+    for i, (w, sm) in enumerate(zip(ws, sms)):
+        for k, v in w.state().items():
+            out["w%d_state_%s" % (i, k)] = v
+        for f in SUMMARY_FIELDS:
+            out["w%d_summary_%s" % (i, f)] = np.array(getattr(sm, f))
+        rows = sm.rows()
+        for f in TRACE_FIELDS:
+            out["w%d_trace_%s" % (i, f)] = np.array([r[f] for r in rows])
+    bs.close()
+    np.savez(path, **out)
+
+
+# ----------------------------------------------------------------------------------------------------------------- test side
+def _solve_in_child(name, path, env):
+    e = dict(os.environ)
+    for k in (KNOB, "SWF_NO_CLIQUE_PACK", "SWF_FULL_FINAL_ELIM", "SWF_NO_SPEC_EVAL"):
+        e.pop(k, None)
+    e["SWF_NO_LAT_FUSE"] = "1"
+    e.update(env)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), name, path], env=e, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, "\n".join((r.stdout + r.stderr).splitlines()[-25:])
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _assert_same_bytes(a, b, keys=None):
+    assert sorted(a) == sorted(b)
+    for k in sorted(a) if keys is None else keys:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["dogleg", "lm", "constant_pose", "even_odd_k", "early_stop", "nan_pose", "envelope"])
+def test_matrix_core_cliques_equal_valu_cliques_bitwise(name, tmp_path):
+    mm = _solve_in_child(name, str(tmp_path / "mm.npz"), {})
+    valu = _solve_in_child(name, str(tmp_path / "valu.npz"), {KNOB: "1"})
+    n_win = len([k for k in mm if k.endswith("_summary_num_iterations")])
+    nit = [int(mm["w%d_summary_num_iterations" % i]) for i in range(n_win)]
+    term = [int(mm["w%d_summary_termination" % i]) for i in range(n_win)]
+    print(name, "iterations per window:", nit, "termination:", term)
+    if name == "nan_pose":
+        # the neighbours' bytes, and the failed window's summary; the failed window itself is NaN through and through, and which NaN
+        # (sign, payload) an instruction hands on is not part of the contract
+        keys = [k for k in sorted(mm) if not k.startswith("w1_") or k.startswith("w1_summary_")]
+        assert len(keys) < len(mm)
+        _assert_same_bytes(mm, valu, keys)
+        assert not np.all(np.isfinite(mm["w1_trace_cost"])) or term[1] != term[0], (term, mm["w1_trace_cost"])
+        for i in (0, 2):
+            assert all(np.all(np.isfinite(mm[k])) for k in mm if k.startswith("w%d_state_" % i) or k in ("w%d_trace_cost" % i, "w%d_trace_gradient_max_norm" % i)), i
+            assert nit[i] > 1, nit
+        return
+    _assert_same_bytes(mm, valu)
+    assert any(k.endswith("_elim_S") for k in mm)
+    assert all(np.all(np.isfinite(mm[k])) for k in mm if k.endswith("_trace_gradient_max_norm") or k.endswith("_elim_S"))
+    assert min(nit) > 1, nit                                                       # the solves ran: the comparison is of more than one linearisation
+    if name == "early_stop":
+        assert max(nit[1], nit[2], nit[3]) < min(nit[0], nit[4]), nit             # the case is a case: some windows stopped before the others
+
+
+if __name__ == "__main__":
+    _child(sys.argv[1], sys.argv[2])
