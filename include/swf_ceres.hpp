@@ -27,6 +27,7 @@
 //   MarginalizationFactor(info)                 R/factor/marginalization_factor.h:104-110 -> swf_add_linear_prior (from a
 //                                                                                        MarginalizationInfo* or from J, r0, x0)
 //   ImuIntegrate() + IMUProcess()               R/swf/swf_imu.cpp:117-213             -> swf_imu_frame_batch (ImuIntegrate below)
+//   initFramePoseByPnP() + solvePoseByPnP()     R/feature/feature_manager.cpp:164-243 -> swf_pnp_frame_batch (InitFramePoseByPnP below)
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
@@ -881,6 +882,51 @@ inline bool ImuIntegrate(const Pairs& accVector, const Pairs& gyrVector, double 
         P(k) = pred[k]; V(k) = pred[12 + k];
         acc_0(k) = out->cut[(size_t)used * 7 + 1 + k]; gyr_0(k) = out->cut[(size_t)used * 7 + 4 + k];
         for (int j = 0; j < 3; j++) R(k, j) = pred[3 + 3 * k + j];
+    }
+    return true;
+}
+
+// The pose of a new image frame from the landmarks it observes: FeatureManager::initFramePoseByPnP with solvePoseByPnP
+// (R/feature/feature_manager.cpp:164-243) for one frame on the device (swf_pnp_frame_batch with one frame and flag bit 0: the points
+// pass through float, as the reference's cv::Point3f / Point2f do; a caller with many streams builds the same arrays and makes one call).
+//   frameCnt, Ps, Rs, tic, ric, Pbg   the reference's arguments (operator()(i), operator()(i, j)); Ps / Rs[frameCnt - 1] is the guess
+//   pts3D, pts2D                      what the loop of :210-228 collects (members x, y, z / x, y); that loop stays with the caller
+//   threshold                         8.0 / FOCAL_LENGTH in the reference; iterations 100, confidence 0.99
+// Returns true and writes Ps / Rs[frameCnt] on SWF_PNP_OK / SWF_PNP_UNREFINED; otherwise (frameCnt <= 0 included) both are untouched,
+// as in the reference.  out, when given, receives the codes and the inlier mask.
+struct PnpFrameResult {
+    int info = -1, n_inliers = 0, best = -1, n_iters = 0;
+    std::vector<uint8_t> inlier;
+};
+template <class V3, class M3, class Pts3, class Pts2>
+inline bool InitFramePoseByPnP(int frameCnt, V3 Ps[], M3 Rs[], const V3 tic[], const M3 ric[], const V3& Pbg, const Pts3& pts3D,
+                               const Pts2& pts2D, double threshold, PnpFrameResult* out = nullptr, uint64_t seed = 0,
+                               int32_t iterations = 100, double confidence = 0.99) {
+    if (frameCnt <= 0 || pts3D.size() != pts2D.size()) return false;
+    const int32_t n = (int32_t)pts3D.size(), first[2] = { 0, n };
+    std::vector<double> pw((size_t)(n + 1) * 3, 0.0), uv((size_t)(n + 1) * 2, 0.0);
+    for (int32_t i = 0; i < n; i++) {
+        pw[(size_t)i * 3] = pts3D[(size_t)i].x; pw[(size_t)i * 3 + 1] = pts3D[(size_t)i].y; pw[(size_t)i * 3 + 2] = pts3D[(size_t)i].z;
+        uv[(size_t)i * 2] = pts2D[(size_t)i].x; uv[(size_t)i * 2 + 1] = pts2D[(size_t)i].y;
+    }
+    double pp[3], rp[9], t[3], r[9], pbg[3], po[3], ro[9];
+    for (int k = 0; k < 3; k++) {
+        pp[k] = Ps[frameCnt - 1](k); t[k] = tic[0](k); pbg[k] = Pbg(k);
+        for (int j = 0; j < 3; j++) { rp[3 * k + j] = Rs[frameCnt - 1](k, j); r[3 * k + j] = ric[0](k, j); }
+    }
+    std::vector<uint8_t> inl((size_t)n + 1, 0);
+    int32_t ni = 0, best = -1, nit = 0, info = -1;
+    if (swf_pnp_frame_batch(1, first, pw.data(), uv.data(), pp, rp, t, r, pbg, iterations, threshold, confidence, seed, 1, po, ro, &ni,
+                            inl.data(), &best, &nit, &info, nullptr, nullptr, nullptr, 0, nullptr) != SWF_OK) return false;
+    const bool ok = info == SWF_PNP_OK || info == SWF_PNP_UNREFINED;
+    if (out) {
+        out->info = info; out->n_inliers = ok ? ni : 0; out->best = ok ? best : -1; out->n_iters = ok ? nit : 0;
+        inl.resize(ok ? (size_t)n : 0); out->inlier = inl;
+    }
+    if (!ok) return false;
+    for (int k = 0; k < 3; k++) {
+        Ps[frameCnt](k) = po[k];
+        for (int j = 0; j < 3; j++) Rs[frameCnt](k, j) = ro[3 * k + j];
     }
     return true;
 }

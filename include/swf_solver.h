@@ -614,6 +614,53 @@ int swf_dd_select_batch(int32_t n_windows, const int32_t* epoch_first, const int
                         int32_t* pairs, int32_t* counts, int32_t* refs, double* cost, uint8_t* role,
                         int32_t on_device, void* stream);
 
+/* Input producer: the pose of a new image frame from the landmarks it observes — FeatureManager::initFramePoseByPnP with
+ * solvePoseByPnP (R/feature/feature_manager.cpp:164-243) for n_frames independent frames in one launch, one workgroup per frame.
+ * The reference's numerical content is cv::solvePnPRansac(pts3D, pts2D, I, -, rvec, t, true, 100, 8.0 / FOCAL_LENGTH, 0.99).  Kept of
+ * it: the 5-point model (4 points for a frame of exactly 4), the previous frame's pose as the guess, the threshold on the squared
+ * reprojection error, the confidence and the adaptive iteration count (RANSACUpdateNumIters), the inlier set of the winning hypothesis,
+ * a refinement on the inliers, the pose conversions and the float rounding of the points.  Specified anew, because they are OpenCV
+ * internals:
+ *   sampler    draw j of hypothesis k is x = splitmix64(seed + 64 k + j) (the generator's output function at state x + 0x9E3779B97F4A7C15,
+ *              modulo 2^64), index ((x >> 32) n) >> 32; a draw equal to an earlier index of the sample is skipped; a sample that is
+ *              not complete after 64 draws is an invalid hypothesis.  The frame index is not mixed in.  n == 4: one hypothesis, 0 1 2 3.
+ *   minimal    6 Gauss-Newton steps from the guess over the sample's residuals r = (x/z - u, y/z - v), p_c = R p_w + t, J = [-J_p [R p_w]_x | J_p],
+ *              unpivoted Cholesky of J^T J, R <- Exp(dtheta) R, t <- t + dt.  Invalid on a pivot <= 0, |z| < 1e-12 or a non-finite value:
+ *              count 0, exported rows NaN.  (OpenCV: EPnP, which needs no guess.)
+ *   inliers    z > 0 and |r|^2 <= threshold^2.  (cv::projectPoints has no test on z.)
+ *   scan       k = 0, 1, .. while k < n_iters (iterations at first): a count > max(best count, m - 1) becomes the best and n_iters is
+ *              updated with ep = (n - count) / n; the quotient of the logarithms is rounded to nearest, halves to even.
+ *   refinement 10 Gauss-Newton steps of the same form from the best hypothesis over its inliers, every sum in a fixed order.
+ * Arrays:
+ *   first      [n_frames + 1]             point offsets
+ *   pts_w      [first[n_frames]][3]       the landmarks' world points (ptsInW, :214-218);  pts_uv [..][2] their normalised observations
+ *   Ps_prev    [n_frames][3], Rs_prev [n_frames][9] row-major   Ps / Rs[frameCnt - 1] as the reference passes them
+ *   tic, ric (row-major), pbg             camera extrinsic and the IMU->antenna lever arm
+ *   iterations, threshold, confidence     100, 8.0 / FOCAL_LENGTH, 0.99 in the reference;  1 <= iterations <= SWF_PNP_HMAX
+ *   flags      bit 0: round pts_w, pts_uv through float first, as cv::Point3f / Point2f do
+ *   Ps_out     [n_frames][3], Rs_out [n_frames][9]   the new frame's pose, in the layout swf_triangulate_batch reads
+ *   n_inliers, best, n_iters, info [n_frames];  inlier [first[n_frames]]   the winning hypothesis's index, count and mask
+ *   samples    [n_frames][iterations][5], hyp [n_frames][iterations][12] (R row-major, then t, of cam_T_w), count [n_frames][iterations]:
+ *              stage exports, null when not wanted; a frame of 4 points writes row 0 only
+ * info: SWF_PNP_TOO_FEW (n < 4), SWF_PNP_BAD_INPUT (a non-finite point or previous pose), SWF_PNP_NO_MODEL (no hypothesis with at
+ * least m inliers): the frame writes its info and nothing else, as the reference leaves the pose alone.  SWF_PNP_UNREFINED: the
+ * refinement met a pivot <= 0, |z| < 1e-12 or a non-finite value; the unrefined hypothesis is written.  Without a usable guess the
+ * operator reports SWF_PNP_NO_MODEL where EPnP might have found a pose.
+ * iterations outside 1 .. SWF_PNP_HMAX or (host memory) a frame above SWF_PNP_NMAX points: SWF_E_UNSUPPORTED; null required pointers,
+ * (host memory) a negative or decreasing `first`, a threshold that is not finite and positive, non-finite confidence or extrinsics: SWF_E_INVALID.
+ * With host memory the TOO_FEW / BAD_INPUT frames are found before the device is touched (a call whose frames all fail so needs none).
+ * Device memory: a frame whose offsets are negative, decreasing or above SWF_PNP_NMAX reports info = -1 and writes nothing else.
+ * A frame's result does not depend on the other frames of the call, and a rerun gives the same bits.  on_device as for
+ * swf_preintegrate_batch. */
+enum { SWF_PNP_OK = 0, SWF_PNP_TOO_FEW = 1, SWF_PNP_NO_MODEL = 2, SWF_PNP_UNREFINED = 3, SWF_PNP_BAD_INPUT = 4 };
+#define SWF_PNP_NMAX 1024      /* points per frame */
+#define SWF_PNP_HMAX 128       /* hypotheses */
+int swf_pnp_frame_batch(int32_t n_frames, const int32_t* first, const double* pts_w, const double* pts_uv,
+                        const double* Ps_prev, const double* Rs_prev, const double tic[3], const double ric[9], const double pbg[3],
+                        int32_t iterations, double threshold, double confidence, uint64_t seed, int32_t flags,
+                        double* Ps_out, double* Rs_out, int32_t* n_inliers, uint8_t* inlier, int32_t* best, int32_t* n_iters,
+                        int32_t* info, int32_t* samples, double* hyp, int32_t* count, int32_t on_device, void* stream);
+
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).
  *   Ps [n_frames][3], Rs [n_frames][9] (row-major)  frame positions / rotations as the reference passes them

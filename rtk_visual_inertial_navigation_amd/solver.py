@@ -63,6 +63,7 @@ EXPORTED = [
     "swf_gnss_epoch_solve_batch",
     "swf_dd_select_batch", "swf_batch_select_ambiguity_pairs", "swf_batch_ambiguity_search_selected", "swf_batch_get_ambiguity_pairs",
     "swf_imu_frame_batch", "swf_preintegrate_runs_batch",
+    "swf_pnp_frame_batch",
 ]
 
 
@@ -918,6 +919,52 @@ def imu_frame_batch(raw, t01, seed, state, gyrj_prev, flags, pbg, g_w, noise, fi
                                        v3(pbg), v3(g_w), nz, cut.ctypes.data_as(_pd), pre.ctypes.data_as(_pd), pred.ctypes.data_as(_pd),
                                        info.ctypes.data_as(pi), C.c_int32(0), None), "imu_frame_batch")
     return dict(cut=cut, first=first, pre=pre, pred=pred, info=info)
+
+
+PNP_OK, PNP_TOO_FEW, PNP_NO_MODEL, PNP_UNREFINED, PNP_BAD_INPUT = 0, 1, 2, 3, 4
+PNP_NMAX, PNP_HMAX = 1024, 128
+
+
+def pnp_frame_batch(pts_w, pts_uv, Ps_prev, Rs_prev, tic, ric, pbg, iterations=100, threshold=8.0 / 1000.0, confidence=0.99, seed=0,
+                    flags=1, fill=0.0, stages=False):
+    """FeatureManager::initFramePoseByPnP + solvePoseByPnP (R/feature/feature_manager.cpp:164-243) for a batch of frames on the device
+    (swf_pnp_frame_batch).  pts_w: list of [n_f][3] world points; pts_uv: list of [n_f][2] normalised observations; Ps_prev [n][3],
+    Rs_prev [n][9] (row-major) the previous frame's pose; tic, ric, pbg the extrinsic and the lever arm; flags bit 0: the points pass
+    through float.  Returns dict(Ps, Rs, n_inliers, inlier, first, best, n_iters, info) and, with stages=True, samples [n][H][5],
+    hyp [n][H][12], count [n][H]; inlier is [first[n]], frame f owning first[f] .. first[f + 1].  A frame whose info is PNP_TOO_FEW,
+    PNP_BAD_INPUT or PNP_NO_MODEL leaves its outputs at `fill` (the integer outputs at int(fill), inlier at 255)."""
+    n = len(pts_w)
+    pw = [np.asarray(p, np.float64).reshape(-1, 3) for p in pts_w]
+    uv = [np.asarray(p, np.float64).reshape(-1, 2) for p in pts_uv]
+    first = np.zeros(n + 1, np.int32)
+    for i in range(n):
+        if pw[i].shape[0] != uv[i].shape[0]:
+            raise SwfError("pnp_frame_batch: frame %d has %d world points and %d observations" % (i, pw[i].shape[0], uv[i].shape[0]))
+        first[i + 1] = first[i] + pw[i].shape[0]
+    tot = int(first[n])
+    fw = np.ascontiguousarray(np.concatenate(pw + [np.zeros((1, 3))]))
+    fu = np.ascontiguousarray(np.concatenate(uv + [np.zeros((1, 2))]))
+    pp = np.ascontiguousarray(np.asarray(Ps_prev, np.float64).reshape(n, 3))
+    rp = np.ascontiguousarray(np.asarray(Rs_prev, np.float64).reshape(n, 9))
+    vec = lambda v, k: (C.c_double * k)(*[float(x) for x in np.asarray(v, np.float64).reshape(k)])
+    H = int(iterations)
+    out = dict(Ps=np.full((n, 3), float(fill)), Rs=np.full((n, 9), float(fill)), n_inliers=np.full(n, int(fill), np.int32),
+               inlier=np.full(tot, 255, np.uint8), first=first, best=np.full(n, int(fill), np.int32), n_iters=np.full(n, int(fill), np.int32),
+               info=np.full(n, -1, np.int32))
+    pi = C.POINTER(C.c_int32)
+    ex = [None, None, None]
+    if stages:
+        Hs = max(H, 0)
+        out.update(samples=np.full((n, Hs, 5), int(fill), np.int32), hyp=np.full((n, Hs, 12), float(fill)), count=np.full((n, Hs), int(fill), np.int32))
+        ex = [out["samples"].ctypes.data_as(pi), out["hyp"].ctypes.data_as(_pd), out["count"].ctypes.data_as(pi)]
+    inl = out["inlier"] if tot else np.zeros(1, np.uint8)
+    _chk(lib().swf_pnp_frame_batch(C.c_int32(n), first.ctypes.data_as(pi), fw.ctypes.data_as(_pd), fu.ctypes.data_as(_pd), pp.ctypes.data_as(_pd),
+                                   rp.ctypes.data_as(_pd), vec(tic, 3), vec(ric, 9), vec(pbg, 3), C.c_int32(H), C.c_double(threshold),
+                                   C.c_double(confidence), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_int32(flags),
+                                   out["Ps"].ctypes.data_as(_pd), out["Rs"].ctypes.data_as(_pd), out["n_inliers"].ctypes.data_as(pi),
+                                   inl.ctypes.data_as(C.POINTER(C.c_uint8)), out["best"].ctypes.data_as(pi), out["n_iters"].ctypes.data_as(pi),
+                                   out["info"].ctypes.data_as(pi), ex[0], ex[1], ex[2], C.c_int32(0), None), "pnp_frame_batch")
+    return out
 
 
 def triangulate_batch(Ps, Rs, tic, ric, pbg, start_frame, pt0, pt1, init_depth=5.0):
