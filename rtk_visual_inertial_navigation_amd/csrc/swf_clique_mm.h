@@ -53,16 +53,28 @@ __global__ void __launch_bounds__(64) k_clique_mm(DevBatch B, DevOpt O) {
     if (cidx_ >= B.n_clc[CLS]) return;
     const Clique& C = B.clc_rec[CLS][cidx_];
     WinState& s = B.ws[C.win];
-    if (!s.need_lin) return;
     const int lane = threadIdx.x, li = lane & 15, lk = lane >> 4;
     const int de = C.d_e, df = C.d_f, d = de + df, nrow = C.n_rows, nr4 = (nrow + 3) & ~3;
     const int nt = (d + 15) >> 4;                   // tile rows / columns in use (wave-uniform)
+    // Gate last (round 11): the window's flags, the residual rows and the first PF values per lane of the Jacobian are requested in one
+    // level behind the record; need_lin is tested with them in flight.  Every address is the record's own: row lane < n_rows of g_r at
+    // r_off and element e < n_rows * d of g_J at j_off belong to the clique whether its window runs or not (plan_validate, "cl").
+    const double* gJ = B.g_J + C.j_off;
+    const int tot = nrow * d;
+    const int need = s.need_lin;
+    const double s_mu = s.mu; const bool s_it0 = s.iter == 0;
+    double rl = lane < nrow ? B.g_r[C.r_off + lane] : 0.0;
+    double v0[PF];
+#pragma unroll
+    for (int u = 0; u < PF; u++) { int e = u * 64 + lane; v0[u] = e < tot ? gJ[e] : 0.0; }
+    rl = pinned_d(rl);                              // (held in front of the gate: the compiler would sink the loads behind it)
+#pragma unroll
+    for (int u = 0; u < PF; u++) v0[u] = pinned_d(v0[u]);
+    if (!need) return;
     QST(0);
     {
-        const double* gJ = B.g_J + C.j_off;
-        int tot = nrow * d;
         float rd = 1.0f / (float)nrow;
-        if (lane < nrow) rv[lane] = B.g_r[C.r_off + lane];
+        if (lane < nrow) rv[lane] = rl;
         // zero rows n_rows .. nr4 - 1 and zero columns d .. MAXD - 1: what the k-steps and the tiles read beyond the clique
         for (int e = lane; e < (nr4 - nrow) * MAXD; e += 64) Jc[nrow + e / MAXD][e % MAXD] = 0.0;
         for (int e = lane; e < nrow * (MAXD - d); e += 64) Jc[e % nrow][d + e / nrow] = 0.0;
@@ -70,7 +82,7 @@ __global__ void __launch_bounds__(64) k_clique_mm(DevBatch B, DevOpt O) {
         for (int base = 0; base < tot; base += PF * 64) {
             double v[PF];
 #pragma unroll
-            for (int u = 0; u < PF; u++) { int e = base + u * 64 + lane; v[u] = e < tot ? gJ[e] : 0.0; }
+            for (int u = 0; u < PF; u++) { int e = base + u * 64 + lane; v[u] = base == 0 ? v0[u] : e < tot ? gJ[e] : 0.0; }      // (the first round came with the flag)
 #pragma unroll
             for (int u = 0; u < PF; u++) {
                 int e = base + u * 64 + lane;
@@ -134,7 +146,7 @@ __global__ void __launch_bounds__(64) k_clique_mm(DevBatch B, DevOpt O) {
 #pragma unroll
             for (int j = 0; j < MAXE; j++) {
                 double v = (lane < de && j < de) ? Me[lane][j] : 0.0;
-                if (j == lane) v += s.mu * (lane < de ? damp_diag(O, v, B.jsc + C.e_loc + lane, s.iter == 0) : clampd(v, O.min_diag, O.max_diag));
+                if (j == lane) v += s_mu * (lane < de ? damp_diag(O, v, B.jsc + C.e_loc + lane, s_it0) : clampd(v, O.min_diag, O.max_diag));
                 row[j] = v; row[MAXE + j] = (j == lane) ? 1.0 : 0.0;
             }
             bool bad = false;

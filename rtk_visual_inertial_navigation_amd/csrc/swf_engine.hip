@@ -351,7 +351,7 @@ extern "C" int swf_batch_create(const swf_flat_window* const* windows, int32_t n
     PUT(s_x); PUT(s_loc); PUT(s_ls); PUT(s_joff); PUT(s_ccol);
     PUT(imu_pre); PUT(cp_dat); PUT(pr_dat); PUT(dop_dat); PUT(sp_w); PUT(gx_dat);
     PUT(imu_gf); PUT(sc_gf); PUT(prior_gf); PUT(idp_gf);
-    PUT(sc_jt); PUT(imu_jt);
+    PUT(sc_jt); PUT(imu_jt); PUT(imu_rec);
     PUT(prior_dim); PUT(prior_Joff); PUT(prior_roff); PUT(prior_x0off);
     PUT(prior_Jt);
     PUT(prior_colloc); PUT(prior_colcc); PUT(s_pcol); PUT(s_pxo);
@@ -1808,8 +1808,8 @@ extern "C" int swf_batch_export_jacobian(swf_batch* b, int32_t w, double* r, dou
 }
 
 // The symbolic phase alone, with no device: plan_build + plan_validate for the given chip size and launch-shape knobs (flags: 1 =
-// SWF_NO_LAT_FUSE, 2 = SWF_NO_CHOL_COL); the validator's finding is left in swf_last_error.  corrupt_table 1 .. 7 damages entry
-// corrupt_index of as_src / sch_rec / s_tnz / prior_colloc / loc2x / co_voff / pair_o in this call's own plan before it is validated (the negative control of the validator).
+// SWF_NO_LAT_FUSE, 2 = SWF_NO_CHOL_COL); the validator's finding is left in swf_last_error.  corrupt_table 1 .. 8 damages entry
+// corrupt_index of as_src / sch_rec / s_tnz / prior_colloc / loc2x / co_voff / pair_o / imu_rec in this call's own plan before it is validated (the negative control of the validator).
 // info (may be null), 12 ints: ls_var, ls_qpb, ls_gqpb, ls_folded, lat_fuse, want_aux, want_Linv, want_Wk, asm_programs, n_pch_split, max_red, n_pch.
 extern "C" int swf_debug_plan_check(const swf_flat_window* const* windows, int32_t n, int32_t n_cu, int32_t ls_variant, int32_t ls_qpb, int32_t ls_grad_qpb,
                                     int32_t flags, int32_t corrupt_table, int32_t corrupt_index, int32_t* info) {
@@ -1828,6 +1828,7 @@ extern "C" int swf_debug_plan_check(const swf_flat_window* const* windows, int32
         else if (corrupt_table == 5 && i < B.loc2x.size()) B.loc2x[i] ^= 1;
         else if (corrupt_table == 6 && i < B.co_voff.size()) B.co_voff[i] += 1 << 28;
         else if (corrupt_table == 7 && i < B.pair_o.size()) B.pair_o[i].q_base += 8;
+        else if (corrupt_table == 8 && i < B.imu_rec.size()) B.imu_rec[i].xo[3] ^= 1;
         else return fail(SWF_E_INVALID, "swf_debug_plan_check: nothing to corrupt there");
     }
     if (info) {

@@ -46,6 +46,8 @@ __device__ __forceinline__ double damp_diag(const DevOpt& O, double d, double* j
 // instead of a cost pass at xc followed by a Jacobian pass at the same point (k_decide then turns the accepted candidate into x and
 // the elimination kernels find its Jacobians in place; a rejected dogleg step re-uses the previous reduced system and needs no Jacobian).
 // (spec == 2: the fused step kernel of the latency path — its workgroups formed the candidate themselves and evaluate it ungated)
+// a value held where the statement stands: a load whose result goes through here is issued and waited for in front of it
+__device__ __forceinline__ double pinned_d(double v) { asm volatile("" : "+v"(v)); return v; }
 template <bool JAC> __device__ __forceinline__ bool eval_gate(const DevBatch& B, const WinState& s) { return B.spec == 2 ? true : (JAC && !B.spec) ? s.need_lin != 0 : s.eval_cand != 0; }
 template <bool JAC> __device__ __forceinline__ const double* eval_src(const DevBatch& B) { return (JAC && !B.spec) ? B.x : B.xc; }
 
@@ -341,21 +343,20 @@ __device__ __forceinline__ void imu_unwhitened(const double* pi, const double* s
 // Whitening of one IMU factor by its IMU_LPF lanes:
 // r = SI raw, cost, and (JAC) the whitened Jacobian SI * U written into the clique's dense column-major Jacobian.
 template <bool JAC>
-__device__ __forceinline__ void imu_whiten_store(const DevBatch& B, const GFac& G, int f, bool act, int sub,
+__device__ __forceinline__ void imu_whiten_store(const DevBatch& B, int roff, int jld, int jo0, int jo1, int jo2, int jo3, int f, bool act, int sub,
                                                  const double* SIf, double* Uf, const double* rawf) {
     constexpr int LPF = IMU_LPF;
     // whitened residual: lane k < 15 of each factor's lanes (all within one 16-lane row)
     double rk = 0;
     if (act && sub < 15) {
         for (int k = 0; k < 15; k++) rk += SIf[sub * 15 + k] * rawf[k];
-        if (JAC) B.g_r[G.roff + sub] = rk;
+        if (JAC) B.g_r[roff + sub] = rk;
     }
     double c = grp16_sum((act && sub < 15) ? rk * rk : 0.0);
     if (act && sub == 0) B.g_cost[f] = 0.5 * c;
     if (!JAC || !act) return;
     const int cb[4] = { 0, 6, 15, 21 };
-    // Jacobian block positions of the four parameter blocks, fetched before the products (off the store loop's chain)
-    const int jo0 = B.s_joff[G.slot0], jo1 = B.s_joff[G.slot0 + 1], jo2 = B.s_joff[G.slot0 + 2], jo3 = B.s_joff[G.slot0 + 3];
+    // (jo0 .. jo3: the Jacobian block positions of the four parameter blocks, from the factor's record)
     // whitened Jacobian SI * U: lane c < 30 owns column c, holds it in registers and forms the 15 rows from broadcast
     // SI reads at constant offsets (120 multiply-adds, fully unrolled; SI is upper triangular, k ascending from the row)
     if (sub < 30) {
@@ -377,56 +378,75 @@ __device__ __forceinline__ void imu_whiten_store(const DevBatch& B, const GFac& 
         int col = e / 15, row = e - col * 15;
         int sl = col < 6 ? 0 : col < 15 ? 1 : col < 21 ? 2 : 3;
         int jo = sl == 0 ? jo0 : sl == 1 ? jo1 : sl == 2 ? jo2 : jo3;
-        if (jo >= 0) B.g_J[jo + (col - cb[sl]) * G.jld + row] = Uf[row * 30 + col];
+        if (jo >= 0) B.g_J[jo + (col - cb[sl]) * jld + row] = Uf[row * 30 + col];
     }
 }
 
+// Loads by dependency level, the window's gate last (round 11; the chain it replaces walked imu_gf -> gf -> window flags -> record,
+// slots, constants -> state, and the lane-serial phase walked the first three again):
+//   (1) the factor's flat record (ImuRec, four 16-byte loads; lanes past the last factor take the last factor's);
+//   (2) unconditionally: the window's flags and constants, the lane's share of the pre-integration record (head and square-root
+//       information) and its state value.  Every address follows from the record alone and plan_validate ("imu_rec") holds each
+//       against its array with the full extent read here, so the loads are in bounds whether the gate is open or not.
+// The gate then decides what is staged; each factor's act goes to LDS for the lane-serial phase.
 template <bool JAC>
 __device__ __forceinline__ void d_eval_imu(const DevBatch& B, int bid) {
     constexpr int LPF = IMU_LPF;
+    constexpr int NPR = (SWF_PRE_SQRTINFO + LPF - 1) / LPF, NSI = (225 + LPF - 1) / LPF;
     __shared__ double SI[IMU_FPB][225];
     __shared__ double U[JAC ? IMU_FPB : 1][JAC ? 450 : 1];    // Jacobian scratch: linearisation only
     __shared__ double raw[IMU_FPB][16];
     __shared__ double st[IMU_FPB][32];
     __shared__ double pr[IMU_FPB][SWF_PRE_SQRTINFO + 6];     // record head (dp .. gyr_j) | pbg | gw, staged by the factor's 16 lanes
+    __shared__ int actf[IMU_FPB];                            // the factor is evaluated (valid, gate open): for the lane-serial phase
     int tid = threadIdx.x, fl = tid / LPF, sub = tid % LPF;
     int q = bid * IMU_FPB + fl;
     bool valid = q < B.n_imu;
-    int f = B.imu_gf[valid ? q : B.n_imu - 1];
-    const GFac& G = B.gf[f];
-    const WinState& s = B.ws[G.win];
-    bool act = valid && eval_gate<JAC>(B, s);
-    const WinRec& W = B.win[G.win];
+    const int4* rp = (const int4*)(B.imu_rec + (valid ? q : B.n_imu - 1));       // 0 <= index < n_imu = the records
+    const int4 r0 = rp[0], r1 = rp[1], rx = rp[2], rj = rp[3];
+    const int win = r0.x, f = r0.y, roff = r0.z, jld = r1.x;
+    const WinState& s = B.ws[win];                           // win < n_win (imu_rec)
+    const WinRec& W = B.win[win];
     const double* xs = eval_src<JAC>(B);
-    const double* pre = B.imu_pre + (size_t)G.data * SWF_PRE_DOUBLES;
+    const double* pre = B.imu_pre + (size_t)r0.w * SWF_PRE_DOUBLES;              // the whole record lies inside imu_pre (imu_rec)
+    const int need = s.need_lin, cand = s.eval_cand;
+    double vpr[NPR], vsi[NSI];
+#pragma unroll
+    for (int u = 0; u < NPR; u++) { const int k = sub + u * LPF; vpr[u] = pre[k < SWF_PRE_SQRTINFO ? k : SWF_PRE_SQRTINFO - 1]; }
+#pragma unroll
+    for (int u = 0; u < NSI; u++) { const int k = sub + u * LPF; vsi[u] = pre[SWF_PRE_SQRTINFO + (k < 225 ? k : 224)]; }
+    const double wc = sub < 3 ? W.pbg[sub] : W.gw[sub < 6 ? sub - 3 : 0];
+    double vst;
+    {
+        const int k = sub;                                   // LPF = 32 lanes: one of the 7 + 9 + 7 + 9 state values each
+        const int sl = k < 7 ? 0 : k < 16 ? 1 : k < 23 ? 2 : 3;
+        const int o = k < 7 ? k : k < 16 ? k - 7 : k < 23 ? k - 16 : k - 23;
+        const int xo = sl == 0 ? rx.x : sl == 1 ? rx.y : sl == 2 ? rx.z : rx.w;
+        vst = xs[xo + o];                                    // xo + 7 / + 9 <= n_x (imu_rec)
+    }
+    static_assert(LPF == 32, "d_eval_imu: one state value per lane");
+    bool act = valid && (B.spec == 2 ? true : (JAC && !B.spec) ? need != 0 : cand != 0);     // eval_gate<JAC>, from the values fetched above
+    if (sub == 0) actf[fl] = act ? 1 : 0;
     if (act) {
-        for (int k = sub; k < SWF_PRE_SQRTINFO; k += LPF) pr[fl][k] = pre[k];
-        if (sub < 3) { pr[fl][SWF_PRE_SQRTINFO + sub] = W.pbg[sub]; pr[fl][SWF_PRE_SQRTINFO + 3 + sub] = W.gw[sub]; }
+#pragma unroll
+        for (int u = 0; u < NPR; u++) { const int k = sub + u * LPF; if (k < SWF_PRE_SQRTINFO) pr[fl][k] = vpr[u]; }
+        if (sub < 6) pr[fl][SWF_PRE_SQRTINFO + sub] = wc;
         if (JAC) for (int k = sub; k < 450; k += LPF) U[JAC ? fl : 0][k] = 0.0;          // the serial lane only fills the non-zero blocks
-        for (int k = sub; k < 225; k += LPF) SI[fl][k] = pre[SWF_PRE_SQRTINFO + k];
-        for (int k = sub; k < 32; k += LPF) {
-            int sl = k < 7 ? 0 : k < 16 ? 1 : k < 23 ? 2 : 3;
-            int o = k < 7 ? k : k < 16 ? k - 7 : k < 23 ? k - 16 : k - 23;
-            st[fl][k] = xs[B.s_x[G.slot0 + sl] + o];
-        }
+#pragma unroll
+        for (int u = 0; u < NSI; u++) { const int k = sub + u * LPF; if (k < 225) SI[fl][k] = vsi[u]; }
+        st[fl][sub] = vst;
     }
     __syncthreads();
     // lanes 0..7 of each wave: one factor each, wave p = part p (residual-only evaluation: part 0 alone)
     if ((tid & 63) < IMU_FPB && (JAC || tid < 64)) {
         int part = tid >> 6, fq = tid & 63;
-        int q2 = bid * IMU_FPB + fq;
-        if (q2 < B.n_imu) {
-            const GFac& G2 = B.gf[B.imu_gf[q2]];
-            const WinState& s2 = B.ws[G2.win];
-            if (eval_gate<JAC>(B, s2)) {
-                imu_unwhitened(st[fq], st[fq] + 7, st[fq] + 16, st[fq] + 23, pr[fq],
-                               pr[fq] + SWF_PRE_SQRTINFO, pr[fq] + SWF_PRE_SQRTINFO + 3, raw[fq], U[JAC ? fq : 0], JAC, part);
-            }
+        if (actf[fq]) {
+            imu_unwhitened(st[fq], st[fq] + 7, st[fq] + 16, st[fq] + 23, pr[fq],
+                           pr[fq] + SWF_PRE_SQRTINFO, pr[fq] + SWF_PRE_SQRTINFO + 3, raw[fq], U[JAC ? fq : 0], JAC, part);
         }
     }
     __syncthreads();
-    (void)W;
-    imu_whiten_store<JAC>(B, G, f, act, sub, SI[fl], U[JAC ? fl : 0], raw[fl]);
+    imu_whiten_store<JAC>(B, roff, jld, rj.x, rj.y, rj.z, rj.w, f, act, sub, SI[fl], U[JAC ? fl : 0], raw[fl]);
 }
 
 template <bool JAC>

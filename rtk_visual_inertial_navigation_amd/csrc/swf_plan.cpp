@@ -763,6 +763,14 @@ int plan_jt_records(Plan& B, std::string& err) {
     };
     B.sc_jt = jt_recs(B.sc_gf); B.imu_jt = jt_recs(B.imu_gf);
     if (!fits) return refuse(err, SWF_E_UNSUPPORTED, "scalar / IMU factor with more than JT_MAXSLOT parameter blocks");
+    // flat evaluation records of the IMU factors (ImuRec, swf_records.h): an IMU factor has its four slots, pose i, speed-bias i, pose j, speed-bias j
+    B.imu_rec.assign(B.imu_gf.size(), ImuRec{});
+    for (size_t q = 0; q < B.imu_gf.size(); q++) {
+        const GFac& G = B.gf[(size_t)B.imu_gf[q]];
+        ImuRec& r = B.imu_rec[q];
+        r.win = G.win; r.f = B.imu_gf[q]; r.roff = G.roff; r.data = G.data; r.jld = G.jld;
+        for (int t = 0; t < 4; t++) { const bool has = t < G.nslot; r.xo[t] = has ? B.s_x[(size_t)G.slot0 + t] : 0; r.joff[t] = has ? B.s_joff[(size_t)G.slot0 + t] : -1; }
+    }
     return SWF_OK;
 }
 
@@ -1067,6 +1075,22 @@ int plan_validate(const Plan& B, std::string& err) {
             NEED(in(r.f, 0, n_gf) && r.f == list[q] && in(r.win, 0, n) && r.roff >= 0 && r.roff + r.nres <= B.r_tot && in(r.nslot, 0, JT_MAXSLOT + 1), pass ? "imu_jt" : "sc_jt", q);
             for (int t = 0; t < JT_MAXSLOT; t++)
                 NEED(r.loc[t] >= -1 && r.loc[t] + r.ls[t] <= B.n_loc && (r.joff[t] == -1 || (r.loc[t] >= 0 && r.joff[t] >= 0 && r.joff[t] + (long long)(r.ls[t] - 1) * r.jld + r.nres <= B.j_tot)) && (t < r.nslot || r.joff[t] == -1), pass ? "imu_jt" : "sc_jt", q);
+        }
+    }
+    // the IMU evaluation records: every field against the factor it copies, and against its array with the FULL extent a lane of
+    // d_eval_imu touches whether the window's gate is open or not (15 residual rows, the whole pre-integration record, 7 / 9 state
+    // values per slot, 6 / 9 Jacobian columns of 15 rows per slot)
+    NEED(B.imu_rec.size() == B.imu_gf.size() && B.imu_pre.size() % SWF_PRE_DOUBLES == 0, "imu_rec", B.imu_rec.size());
+    for (size_t q = 0; q < B.imu_rec.size(); q++) {
+        const ImuRec& r = B.imu_rec[q];
+        NEED(in(r.f, 0, n_gf) && r.f == B.imu_gf[q], "imu_rec", q);
+        const GFac& G = B.gf[r.f];
+        NEED(G.type == GF_IMU && G.nslot == 4 && G.nres == 15 && r.win == G.win && in(r.win, 0, n) && r.roff == G.roff && r.roff >= 0 && (long long)r.roff + 15 <= B.r_tot, "imu_rec", q);
+        NEED(r.data == G.data && r.data >= 0 && ((long long)r.data + 1) * SWF_PRE_DOUBLES <= (long long)B.imu_pre.size() && r.jld == G.jld && r.jld >= 0, "imu_rec", q);
+        for (int t = 0; t < 4; t++) {
+            const long long gs = (t & 1) ? 9 : 7, ls = (t & 1) ? 9 : 6;
+            NEED(r.xo[t] == B.s_x[(size_t)G.slot0 + t] && r.xo[t] >= 0 && r.xo[t] + gs <= B.n_x, "imu_rec", q);
+            NEED(r.joff[t] == B.s_joff[(size_t)G.slot0 + t] && (r.joff[t] == -1 || (r.joff[t] >= 0 && r.joff[t] + (ls - 1) * r.jld + 15 <= B.j_tot)), "imu_rec", q);
         }
     }
     {

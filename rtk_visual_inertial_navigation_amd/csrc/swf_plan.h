@@ -82,6 +82,7 @@ struct Plan {
     std::vector<int> sch_c0, sch_rec, sch_km;
     std::vector<int> fsb_rec;
     std::vector<JtRec> sc_jt, imu_jt;
+    std::vector<ImuRec> imu_rec;
     std::vector<double> prior_Jt;
     std::vector<int> prior_colloc, prior_colcc, s_pcol, s_pxo, cv_loc;
     std::vector<Pair> pair_d, pair_o;

@@ -65,6 +65,16 @@ struct alignas(16) JtRec {
 };
 static_assert(sizeof(JtRec) == 96, "JtRec: six 16-byte loads");
 
+// flat record of an IMU factor for its evaluation (d_eval_imu, swf_kernels.h), one per entry of imu_gf: what imu_gf -> gf -> s_x /
+// s_joff hold about the factor, in four 16-byte loads.  Slots: pose i, speed-bias i, pose j, speed-bias j.
+struct alignas(16) ImuRec {
+    int win, f, roff, data;       // window; index in gf (g_cost); first residual row in g_r; record in imu_pre
+    int jld, pad0, pad1, pad2;    // column stride of the factor's Jacobian blocks in g_J
+    int xo[4];                    // state offset of each slot's block (7, 9, 7, 9 doubles)
+    int joff[4];                  // g_J offset of each slot's block (6, 9, 6, 9 columns of 15 rows), -1 where the slot has none
+};
+static_assert(sizeof(ImuRec) == 64, "ImuRec: four 16-byte loads");
+
 // ---- clique: a group-0 block (or none) + the factors touching it + its reduced neighbours
 struct Clique {
     int win;
@@ -171,6 +181,7 @@ struct DevBatch {
     int n_idp; const int* idp_gf;              // two-row projection factors of the generic path: inverse-depth (GF_IDP) and world-point (GF_PROJX) ones (also members of sc_gf for the J v products)
     int n_sc;  const int* sc_gf;
     const JtRec* sc_jt; const JtRec* imu_jt;    // flat J v records, one per entry of sc_gf / imu_gf
+    const ImuRec* imu_rec;                     // flat evaluation records, one per entry of imu_gf
     int n_prior; const int* prior_gf;
     // priors.  A prior of more than PRIOR_SPLIT_DIM rows is evaluated by one workgroup per chunk of PRIOR_CHUNK rows (its n x n record is
     // n^2 doubles through ONE compute unit otherwise: 553 KB, 19 us per pass, for the 263-dimension marginalisation prior of BASELINE
