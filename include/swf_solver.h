@@ -358,7 +358,8 @@ int swf_batch_timing(swf_batch* b, swf_timing* out);
  *   bias     [n_intervals][6]         linearisation biases ba, bg
  *   noise    ACC_N, GYR_N, ACC_W, GYR_W (yaml; R/parameter/parameters.cpp)
  *   pre      [n_intervals][SWF_PRE_DOUBLES] records, the layout swf_add_imu / swf_flat_window::imu_pre take.
- *            A covariance that is not positive definite (an interval with no push_back) leaves sqrt_info zero.
+ *            A covariance without full rank (an interval with no push_back or with one: rank 12; all-zero noise densities) leaves
+ *            sqrt_info zero: a pivot of its factorisation at or below 2^-20 of its own diagonal entry refuses it.
  * on_device = 0: all pointers are host memory; the call copies in, runs, copies out and synchronises.
  * on_device = 1: all pointers are device memory; the kernel is enqueued on `stream` and the call returns.
  * ===================================================================================== */

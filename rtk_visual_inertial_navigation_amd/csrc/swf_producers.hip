@@ -99,6 +99,7 @@ __device__ __forceinline__ void apply_F(const StepMats& S, double* x) {
 
 #define PI_GROUPS 4            // intervals per wavefront (16 lanes each: lane c < 15 owns column c of the Jacobian and of the covariance)
 #define PI_TLD 17              // padded row of the transpose buffer
+#define PI_RANK_TOL 0x1p-20    // a pivot of the covariance's factorisation at or below this share of its diagonal entry: rank-deficient
 
 // The cursor of PI_RUNS: row after row of run after run.  next() is called only while rows are left, so it ends inside the list; a
 // run that leaves samples[n_samples] counts as empty.
@@ -387,11 +388,18 @@ __global__ void __launch_bounds__(64) k_preintegrate(PreintArgs A) {
         }
     }
     // get_sqrtinfo: cov = R R^T with R upper triangular, built from the last column backwards; lane k holds column k (= row k) of
-    // the trailing matrix, so the pivot column comes from lane j by row broadcast and R[k][j] from the lane's own row j
+    // the trailing matrix, so the pivot column comes from lane j by row broadcast and R[k][j] from the lane's own row j.
+    // A covariance without full rank is refused (sqrt_info zero): one push_back leaves V Q V^T with rank 12 (rows 0-2 of V are dt / 2
+    // times rows 6-8) whatever the samples are, and its last pivots are rounding residue of either sign, so the test is the pivot
+    // against its own diagonal entry before the elimination, not its sign.  A regular covariance keeps every pivot above 1 / (its
+    // scaled condition number) of that entry: 1 / 30 on IMU data.
     bool ok = true;
+    double diag0 = 0.0;                                     // this lane's diagonal entry of the covariance
+#pragma unroll
+    for (int i = 0; i < 15; i++) if (i == c) diag0 = cc[i];
 #define PI_CHOL_STEP(J) { \
-        double d = row_bcast<J>(cc[J]); \
-        ok = ok && (d > 0) && (d < 1e300); \
+        double d = row_bcast<J>(cc[J]), d0 = row_bcast<J>(diag0); \
+        ok = ok && (d > PI_RANK_TOL * d0) && (d < 1e300); \
         double sd = sqrt(ok ? d : 1.0), inv = 1.0 / sd; \
         double rk = cc[J] * inv; \
         _Pragma("unroll") for (int i = 0; i < J; i++) { \
