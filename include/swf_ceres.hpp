@@ -28,6 +28,7 @@
 //                                                                                        MarginalizationInfo* or from J, r0, x0)
 //   ImuIntegrate() + IMUProcess()               R/swf/swf_imu.cpp:117-213             -> swf_imu_frame_batch (ImuIntegrate below)
 //   initFramePoseByPnP() + solvePoseByPnP()     R/feature/feature_manager.cpp:164-243 -> swf_pnp_frame_batch (InitFramePoseByPnP below)
+//   rejectWithF() + undistortedPts() + ptsVelocity()  R/feature/feature_tracker.cpp:265-294, :334-376 -> swf_track_reject_batch (RejectWithF below)
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
@@ -929,6 +930,59 @@ inline bool InitFramePoseByPnP(int frameCnt, V3 Ps[], M3 Rs[], const V3 tic[], c
         for (int j = 0; j < 3; j++) Rs[frameCnt](k, j) = ro[3 * k + j];
     }
     return true;
+}
+
+// The geometric gate of the feature tracker: FeatureTracker::rejectWithF (R/feature/feature_tracker.cpp:265-294) with undistortedPts
+// (:334-343) and ptsVelocity (:345-376) for one frame pair on the device (swf_track_reject_batch with one pair and flag bit 0: the
+// points pass through float wherever the reference holds a cv::Point2f; a caller with many streams builds the same arrays and makes one
+// call).
+//   cur_pts, prev_pts          the tracker's vectors of the same tracks (members x, y)
+//   cam                        fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 of the PINHOLE_FULL camera; col, row, focal: the image size and FOCAL_LENGTH
+//   f_threshold, dt            F_THRESHOLD; cur_time - prev_time
+// Returns true on SWF_TRK_OK: out->status is then what cv::findFundamentalMat's status is to the reference, for ReduceVector below.
+// With fewer than 8 tracks (SWF_TRK_TOO_FEW, the reference skips the gate) or without a model it returns false and out->status is
+// empty; un_cur, un_prev and velocity are filled in all three cases.  KLT, setMask, goodFeaturesToTrack, the id maps and track_cnt stay
+// with the caller.
+struct RejectWithFResult {
+    int info = -1, n_inliers = 0, best = -1, n_iters = 0;
+    std::vector<uint8_t> status;
+    std::vector<double> un_cur, un_prev, velocity;      // [n][2]
+};
+template <class Pts>
+inline bool RejectWithF(const Pts& cur_pts, const Pts& prev_pts, const double cam[12], int col, int row, double focal, double f_threshold,
+                        double dt, RejectWithFResult* out, uint64_t seed = 0, int32_t iterations = 1000, double confidence = 0.99) {
+    if (!out || cur_pts.size() != prev_pts.size()) return false;
+    const int32_t n = (int32_t)cur_pts.size(), first[2] = { 0, n };
+    std::vector<double> c((size_t)(n + 1) * 2, 0.0), p((size_t)(n + 1) * 2, 0.0);
+    for (int32_t i = 0; i < n; i++) {
+        c[(size_t)i * 2] = cur_pts[(size_t)i].x; c[(size_t)i * 2 + 1] = cur_pts[(size_t)i].y;
+        p[(size_t)i * 2] = prev_pts[(size_t)i].x; p[(size_t)i * 2 + 1] = prev_pts[(size_t)i].y;
+    }
+    std::vector<uint8_t> st((size_t)n + 1, 0);
+    out->un_cur.assign((size_t)(n + 1) * 2, 0.0); out->un_prev.assign((size_t)(n + 1) * 2, 0.0); out->velocity.assign((size_t)(n + 1) * 2, 0.0);
+    int32_t ni = 0, best = -1, nit = 0, info = -1;
+    const int rc = swf_track_reject_batch(1, first, c.data(), p.data(), cam, col, row, focal, &dt, iterations, f_threshold, confidence, seed, 1,
+                                          st.data(), nullptr, &ni, &best, &nit, &info, nullptr, out->un_cur.data(), out->un_prev.data(),
+                                          out->velocity.data(), nullptr, nullptr, nullptr, 0, nullptr);
+    const bool ok = rc == SWF_OK && info == SWF_TRK_OK;
+    const bool lifted = rc == SWF_OK && info != SWF_TRK_BAD_INPUT;
+    out->info = rc == SWF_OK ? info : -1; out->n_inliers = ok ? ni : 0; out->best = ok ? best : -1; out->n_iters = ok ? nit : 0;
+    st.resize(ok ? (size_t)n : 0); out->status = st;
+    out->un_cur.resize(lifted ? (size_t)n * 2 : 0); out->un_prev.resize(lifted ? (size_t)n * 2 : 0); out->velocity.resize(lifted ? (size_t)n * 2 : 0);
+    return ok;
+}
+
+// what the reference's reduceVector (:21-35) does with a status: the kept elements move to the front, in order
+template <class T>
+inline void ReduceVector(std::vector<T>& v, const std::vector<uint8_t>& status) {
+    const size_t n = v.size() < status.size() ? v.size() : status.size();
+    size_t kept = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (!status[i]) continue;
+        if (kept != i) v[kept] = v[i];
+        kept++;
+    }
+    v.resize(kept);
 }
 
 }  // namespace swf_ceres

@@ -662,6 +662,57 @@ int swf_pnp_frame_batch(int32_t n_frames, const int32_t* first, const double* pt
                         double* Ps_out, double* Rs_out, int32_t* n_inliers, uint8_t* inlier, int32_t* best, int32_t* n_iters,
                         int32_t* info, int32_t* samples, double* hyp, int32_t* count, int32_t on_device, void* stream);
 
+/* Input producer: the geometric gate between tracked pixels and the estimator — FeatureTracker::rejectWithF with undistortedPts and
+ * ptsVelocity (R/feature/feature_tracker.cpp:265-294, :334-376) for n_pairs independent frame pairs in one launch, one workgroup per
+ * pair.  The reference's numerical content is PinholeFullCamera::liftProjective (C/src/camera_models/PinholeFullCamera.cc:535-607) and
+ * cv::findFundamentalMat(un_cur, un_prev, FM_RANSAC, F_THRESHOLD, 0.99, status).  Kept of the latter: the virtual-camera pixels, the
+ * symmetric epipolar distance against the squared threshold, the confidence and the adaptive iteration count (RANSACUpdateNumIters),
+ * the status of the winning hypothesis, no refit.  Specified anew:
+ *   lift       x0 = p.x / fx - cx / fx (y alike), then exactly nine fixed-point steps in the order of :574-581: r2, icdist =
+ *              (1 + ((k6 r2 + k5) r2 + k4) r2) / (1 + ((k3 r2 + k2) r2 + k1) r2), deltaX, deltaY, x = (x0 - deltaX) icdist, y alike
+ *              (the reference's loop ends only by its counter).  Every operation rounds once.  u = focal x + col / 2, v = focal y + row / 2.
+ *   sampler    that of swf_pnp_frame_batch with 8 indices: draw j of hypothesis k is x = splitmix64(seed + 64 k + j), index
+ *              ((x >> 32) n) >> 32, repeats skipped, invalid when incomplete after 64 draws.  n == 8: one hypothesis, 0 .. 7.
+ *   minimal    the 8-point algorithm (OpenCV's run8Point; FM_RANSAC itself draws 7 points and solves a cubic): each image's sample is
+ *              translated to its centroid and scaled by sqrt(2) / mean distance (invalid below a mean distance of 2^-23); rows
+ *              [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1], m1 = cur, m2 = prev; F0 the unit right null vector (Householder QR of
+ *              the transposed design matrix); the smallest singular value of the 3 x 3 set to 0 (one-sided Jacobi, six sweeps);
+ *              F = T2^T F0 T1, row-major.  A non-finite value makes the hypothesis invalid: count 0, exported row NaN.
+ *   inliers    d2 = (m2^T F m1)^2 / (a^2 + b^2), (a, b, .) = F m1; d1 alike through F^T m2; inlier iff d1 <= thr^2 and d2 <= thr^2.
+ *   scan       k = 0, 1, .. while k < n_iters (iterations at first): a count > max(best count, 7) becomes the best and n_iters is
+ *              updated with 8 model points; the quotient of the logarithms is rounded to nearest, halves to even.
+ * Arrays:
+ *   first      [n_pairs + 1]              point offsets
+ *   cur_px, prev_px [first[n_pairs]][2]   pixel positions of the same tracks in the current and the previous frame
+ *   cam        [12]                       fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 (PINHOLE_FULL);  col, row, focal: 752, 480, FOCAL_LENGTH = 1000
+ *   dt         [n_pairs]                  cur_time - prev_time
+ *   iterations, threshold, confidence     1 <= iterations <= SWF_TRK_HMAX (OpenCV: 1000), F_THRESHOLD = 1.0 px, 0.99
+ *   flags      bit 0: round through float wherever the reference holds a cv::Point2f: the pixel inputs, the virtual-camera pixels, the
+ *              normalised outputs, and the velocity (difference formed in float, divided by dt in double, stored as float)
+ *   status     [first[n_pairs]]           1 = keep;  keep_idx [first[n_pairs]]: the kept indices of a pair (counted from the pair's first
+ *              point) in ascending order from first[k], -1 behind them (reduceVector)
+ *   n_inliers, best, n_iters, info [n_pairs];  F [n_pairs][9] the winning hypothesis
+ *   un_cur, un_prev [..][2]               undistortedPts;  velocity [..][2] = (un_cur - un_prev) / dt (ptsVelocity for an aligned pair)
+ *   samples    [n_pairs][iterations][8], hyp [n_pairs][iterations][9], count [n_pairs][iterations]: stage exports of every hypothesis,
+ *              whatever the scan used; a pair of 8 points writes row 0 only
+ * Every output but info may be null.
+ * info: SWF_TRK_BAD_INPUT (a non-finite pixel or dt, dt <= 0; tested first): the pair writes its info only.  SWF_TRK_TOO_FEW (n < 8,
+ * the reference skips the gate) and SWF_TRK_NO_MODEL (no hypothesis with 8 inliers): un_cur, un_prev and velocity are written, nothing
+ * else.  iterations outside 1 .. SWF_TRK_HMAX or (host memory) a pair above SWF_TRK_NMAX points: SWF_E_UNSUPPORTED; null required
+ * pointers, (host memory) a negative or decreasing `first`, a threshold or focal that is not finite and positive, a non-finite
+ * confidence or cam, fx or fy of 0: SWF_E_INVALID.  With host memory the BAD_INPUT pairs are found before the device is touched.
+ * Device memory: a pair whose offsets are negative, decreasing or above SWF_TRK_NMAX reports info = -1 and writes nothing else.
+ * A pair's result does not depend on the other pairs of the call, and a rerun gives the same bits.  on_device as for
+ * swf_preintegrate_batch. */
+enum { SWF_TRK_OK = 0, SWF_TRK_TOO_FEW = 1, SWF_TRK_NO_MODEL = 2, SWF_TRK_BAD_INPUT = 3 };
+#define SWF_TRK_NMAX 1024      /* points per pair */
+#define SWF_TRK_HMAX 1024      /* hypotheses */
+int swf_track_reject_batch(int32_t n_pairs, const int32_t* first, const double* cur_px, const double* prev_px, const double cam[12],
+                           int32_t col, int32_t row, double focal, const double* dt, int32_t iterations, double threshold,
+                           double confidence, uint64_t seed, int32_t flags, uint8_t* status, int32_t* keep_idx, int32_t* n_inliers,
+                           int32_t* best, int32_t* n_iters, int32_t* info, double* F, double* un_cur, double* un_prev,
+                           double* velocity, int32_t* samples, double* hyp, int32_t* count, int32_t on_device, void* stream);
+
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).
  *   Ps [n_frames][3], Rs [n_frames][9] (row-major)  frame positions / rotations as the reference passes them

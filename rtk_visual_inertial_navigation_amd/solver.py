@@ -64,6 +64,7 @@ EXPORTED = [
     "swf_dd_select_batch", "swf_batch_select_ambiguity_pairs", "swf_batch_ambiguity_search_selected", "swf_batch_get_ambiguity_pairs",
     "swf_imu_frame_batch", "swf_preintegrate_runs_batch",
     "swf_pnp_frame_batch",
+    "swf_track_reject_batch",
 ]
 
 
@@ -964,6 +965,59 @@ def pnp_frame_batch(pts_w, pts_uv, Ps_prev, Rs_prev, tic, ric, pbg, iterations=1
                                    out["Ps"].ctypes.data_as(_pd), out["Rs"].ctypes.data_as(_pd), out["n_inliers"].ctypes.data_as(pi),
                                    inl.ctypes.data_as(C.POINTER(C.c_uint8)), out["best"].ctypes.data_as(pi), out["n_iters"].ctypes.data_as(pi),
                                    out["info"].ctypes.data_as(pi), ex[0], ex[1], ex[2], C.c_int32(0), None), "pnp_frame_batch")
+    return out
+
+
+TRK_OK, TRK_TOO_FEW, TRK_NO_MODEL, TRK_BAD_INPUT = 0, 1, 2, 3
+TRK_NMAX, TRK_HMAX = 1024, 1024
+
+
+def track_reject_batch(cur_px, prev_px, cam, dt, col=752, row=480, focal=1000.0, iterations=1000, threshold=1.0, confidence=0.99, seed=0,
+                       flags=1, fill=0.0, stages=False):
+    """FeatureTracker::rejectWithF with undistortedPts and ptsVelocity (R/feature/feature_tracker.cpp:265-294, :334-376) for a batch of
+    frame pairs on the device (swf_track_reject_batch).  cur_px, prev_px: lists of [n_k][2] pixel positions of the same tracks in the
+    current and the previous frame; cam [12] = fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6; dt [n] = cur_time - prev_time; flags bit 0: round
+    through float wherever the reference holds a cv::Point2f.  Returns dict(status, keep_idx, first, n_inliers, best, n_iters, info, F,
+    un_cur, un_prev, velocity) and, with stages=True, samples [n][H][8], hyp [n][H][9], count [n][H]; the per-point arrays are
+    [first[n]], pair k owning first[k] .. first[k + 1].  A pair whose info is TRK_BAD_INPUT leaves its outputs at `fill` (the integer
+    outputs at int(fill), status at 255); TRK_TOO_FEW and TRK_NO_MODEL write un_cur, un_prev and velocity only."""
+    n = len(cur_px)
+    cp = [np.asarray(p, np.float64).reshape(-1, 2) for p in cur_px]
+    pp = [np.asarray(p, np.float64).reshape(-1, 2) for p in prev_px]
+    if len(pp) != n:
+        raise SwfError("track_reject_batch: %d current and %d previous frames" % (n, len(pp)))
+    first = np.zeros(n + 1, np.int32)
+    for i in range(n):
+        if cp[i].shape[0] != pp[i].shape[0]:
+            raise SwfError("track_reject_batch: pair %d has %d current and %d previous points" % (i, cp[i].shape[0], pp[i].shape[0]))
+        first[i + 1] = first[i] + cp[i].shape[0]
+    tot = int(first[n])
+    fc = np.ascontiguousarray(np.concatenate(cp + [np.zeros((1, 2))]))
+    fp = np.ascontiguousarray(np.concatenate(pp + [np.zeros((1, 2))]))
+    dts = np.ascontiguousarray(np.asarray(dt, np.float64).reshape(n)) if n else np.zeros(1)
+    cm = (C.c_double * 12)(*[float(x) for x in np.asarray(cam, np.float64).reshape(12)])
+    H = int(iterations)
+    pts = max(tot, 1)
+    out = dict(status=np.full(pts, 255, np.uint8), keep_idx=np.full(pts, int(fill), np.int32), first=first,
+               n_inliers=np.full(n, int(fill), np.int32), best=np.full(n, int(fill), np.int32), n_iters=np.full(n, int(fill), np.int32),
+               info=np.full(n, -1, np.int32), F=np.full((n, 9), float(fill)), un_cur=np.full((pts, 2), float(fill)),
+               un_prev=np.full((pts, 2), float(fill)), velocity=np.full((pts, 2), float(fill)))
+    pi = C.POINTER(C.c_int32)
+    ex = [None, None, None]
+    if stages:
+        Hs = max(H, 0)
+        out.update(samples=np.full((n, Hs, 8), int(fill), np.int32), hyp=np.full((n, Hs, 9), float(fill)), count=np.full((n, Hs), int(fill), np.int32))
+        ex = [out["samples"].ctypes.data_as(pi), out["hyp"].ctypes.data_as(_pd), out["count"].ctypes.data_as(pi)]
+    _chk(lib().swf_track_reject_batch(C.c_int32(n), first.ctypes.data_as(pi), fc.ctypes.data_as(_pd), fp.ctypes.data_as(_pd), cm, C.c_int32(col),
+                                      C.c_int32(row), C.c_double(focal), dts.ctypes.data_as(_pd), C.c_int32(H), C.c_double(threshold),
+                                      C.c_double(confidence), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_int32(flags),
+                                      out["status"].ctypes.data_as(C.POINTER(C.c_uint8)), out["keep_idx"].ctypes.data_as(pi),
+                                      out["n_inliers"].ctypes.data_as(pi), out["best"].ctypes.data_as(pi), out["n_iters"].ctypes.data_as(pi),
+                                      out["info"].ctypes.data_as(pi), out["F"].ctypes.data_as(_pd), out["un_cur"].ctypes.data_as(_pd),
+                                      out["un_prev"].ctypes.data_as(_pd), out["velocity"].ctypes.data_as(_pd), ex[0], ex[1], ex[2],
+                                      C.c_int32(0), None), "track_reject_batch")
+    for key in ("status", "keep_idx", "un_cur", "un_prev", "velocity"):
+        out[key] = out[key][:tot]
     return out
 
 
