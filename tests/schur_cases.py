@@ -1,0 +1,105 @@
+"""Seeded windows of tests/test_schur_componentwise.py — TEST INFRASTRUCTURE.
+
+Each is the smallest window that still reaches the code path named next to it.  k_lm_schur's variant is chosen by plan_schur_shape
+(csrc/swf_plan.cpp) from the largest window's tile count nt (nt + 1) / 2, nt = ceil(6 x observing frames / 16): <= 10 tiles (up to 10
+frames) the 4-wave class, <= 36 (up to 21 frames) the 8-wave class, <= 136 (up to 42 frames) the 12-consumer-wave class, beyond that the
+64-frame class.  The count that selects is the number of FRAMES, so K sits one past each threshold and F is cut to what still gives
+tracks of the wanted lengths (synth draws track lengths in [2, K] with mean K / 2)."""
+import numpy as np
+
+from rtk_visual_inertial_navigation_amd import synth
+
+
+def _with_constant(w, pose):
+    from test_clique_mfma_gpu import _with_constant as f
+    return f(w, pose)
+
+
+def _idepth(w, **kw):
+    import idepth_gen
+    return idepth_gen.convert_short_tracks(w, **kw)
+
+
+def _composite():
+    import composite_gen as cg
+    return cg.make_window(np.random.default_rng(191), 5, 2, 8, F=30)
+
+
+# name -> builder.  SCHUR: judged by the full referee (grad, diag, S, rhs, L).
+SCHUR = {
+    # 3 frames, 6 landmarks, VI only: one tile, the 4-wave class; every clique is a one- or two-IMU-factor speed-bias clique
+    "tiny_vi": lambda: synth.make_window(2, K=3, F=6, S=0, seed=7),
+    # the smallest RTK window (>= 5 satellites: position observable): ambiguity and clock scalars in the reduced system
+    "tiny_rtk": lambda: synth.make_window(3, K=4, F=9, S=5, seed=8),
+    # nothing a multiple of 16 / 32 / 64: 7 frames = 42 pose rows (3 row tiles, the last ragged), 33 landmarks (four per wave task: one left over)
+    "ragged": lambda: synth.make_window(3, K=7, F=33, S=12, seed=9),
+    # Doppler rows and the clock-drift column join the speed-bias cliques (S = 6: 36 rows, past the 32-row limit of clique class 1)
+    "doppler": lambda: synth.make_window(3, K=6, F=30, S=6, seed=5, doppler=True),
+    # Doppler with S = 2: the clique stays in class 1 (32 x 46), the shape k_clique_mm takes on the batch path
+    "doppler_class1": lambda: synth.make_window(3, K=5, F=20, S=2, seed=15, doppler=True),
+    # rover-only pseudorange / carrier phase and fixed-integer factors
+    "spp_fixed": lambda: synth.with_spp_and_fixed(synth.make_window(3, K=5, F=14, S=6, seed=4), seed=3, n_fix=3),
+    # inverse-depth landmarks, tracks up to 7: scalar eliminated blocks, cliques within one wavefront
+    "idepth_short": lambda: _idepth(synth.make_window(2, K=8, F=30, S=0, seed=4)),
+    # inverse-depth features tracked over 16 frames: cliques beyond one wavefront, k_clique_big
+    "idepth_long": lambda: _idepth(synth.make_window(2, K=16, F=30, S=0, seed=6), max_track=16),
+    # world-point landmarks whose factors touch a VARIABLE extrinsic: the generic path
+    "var_extrinsic": lambda: synth.with_variable_extrinsic(synth.make_window(2, K=6, F=30, S=0, seed=13)),
+    # cfg5: a dense marginalisation prior over 13 poses (one 78-row factor over 78 columns)
+    "dense_prior": lambda: synth.make_window(5, K=14, F=40, S=4, seed=10),
+    # frames linked only by composite IMU-GNSS factors, landmarks on the same pose blocks
+    "composite_landmarks": _composite,
+    # one pose held constant: 30 x 39 and 15 x 24 cliques, projection factors with a missing block
+    "constant_pose": lambda: _with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1021), pose=2),
+    # 22 observing frames (> 21): 9 row tiles = 45 tiles, the 12-consumer-wave k_lm_schur; tracks of 17 .. 22 span two 16-lane groups
+    "frames_22": lambda: synth.make_window(3, K=22, F=12, S=5, seed=15),
+    # tracks of 33 and 34 observations: four groups, a whole producer wave (34 frames: still the 12-consumer-wave class)
+    "tracks_33": lambda: synth.make_window(2, K=34, F=8, S=0, seed=13),
+    # 43 observing frames (> 42): 17 row tiles = 153 tiles, the 64-frame class
+    "frames_43": lambda: synth.make_window(2, K=43, F=12, S=0, seed=15),
+    # n_red = 256 with a 25-ambiguity tail (also a marginal-prior case).  Seed 22, the window of test_gpu_parity.py's CASES, has one entry of
+    # S that cancels to 3e-11 of its bracket and breaks the no-vacuous-entry condition; seed 23 is the next one and does not
+    "ambiguity_tail": lambda: synth.make_window(3, K=22, F=36, S=25, seed=23, head="ambiguities"),
+    # the dense-prior window with the frames the prior does not hold as parameter_head: a 123-dimension tail (a marginal-prior case)
+    "dense_prior_tail": lambda: synth.make_window(5, K=14, F=40, S=4, seed=10, head="frames"),
+    # the smallest window with a tail to marginalise onto
+    "tiny_tail": lambda: synth.make_window(3, K=4, F=9, S=5, seed=8, head="ambiguities"),
+}
+
+# M_L only: the Cholesky kernels by n_red.  No Schur referee: one longdouble product L L^T against the implementation's own S.
+FACTOR = {
+    "n_red_241": lambda: synth.make_window(3, K=22, F=40, S=10, seed=21),     # the first window of k_chol_rr4<16> (240 < n_red <= 256)
+    "n_red_251": lambda: synth.make_window(3, K=23, F=30, S=5, seed=23),      # ragged last tile
+    "n_red_256": lambda: synth.make_window(3, K=22, F=36, S=25, seed=22, head="ambiguities"),      # the largest register-resident one
+    "n_red_278": lambda: synth.make_window(3, K=26, F=40, S=5, seed=11),      # > 256: the streaming Cholesky
+    "n_red_550": lambda: synth.make_window(3, K=52, F=48, S=4, seed=16),      # > 512: k_chol_big beyond the two-panel kernel's range
+}
+FACTOR_N_RED = {"n_red_241": 241, "n_red_251": 251, "n_red_256": 256, "n_red_278": 278, "n_red_550": 550}
+
+# marginal prior (swf_batch_marginalize, Cholesky form): the cases of SCHUR with a parameter_head tail
+MARGINAL = ("dense_prior_tail", "ambiguity_tail", "tiny_tail")
+
+# the batch path: 33 windows (33 x 8 > the CU count: no latency path, no environment knob); windows 0 .. 5 distinct, the rest copies of 5
+BATCH_HEAD = ("tiny_vi", "tiny_rtk", "ragged", "doppler_class1", "constant_pose", "spp_fixed")
+BATCH_N = 33
+
+# launch-shape knobs of k_lm_schur on the ragged case (read when the batch is created)
+KNOBS = ({"SWF_LS_QPB": "1"}, {"SWF_LS_QPB": "16"}, {"SWF_LS_VARIANT": "1"}, {"SWF_LS_VARIANT": "2", "SWF_LS_QPB": "16"})
+
+
+def window(name):
+    return (SCHUR.get(name) or FACTOR[name])()
+
+
+def tail_dim(w):
+    """local dimension of the window's parameter_head tail: its last n_tail blocks in elimination order"""
+    _, l = w.block_sizes()
+    return int(sum(l[b] for b in w.a["order_block"][len(w.a["order_block"]) - w.n_tail:]))
+
+
+def shape(w):
+    """(observing frames, longest track) of a window's projection factors (0, 0 without any)"""
+    pi = w.a["proj_idx"].reshape(-1, 3)
+    if not pi.size:
+        return 0, 0
+    return int(np.unique(pi[:, 0]).size), int(np.bincount(pi[:, 2]).max())
