@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "swf_ddselect.h"
+#include "swf_stage.h"
 // Floating-point contraction is off in this translation unit: the kernel has no product, and every sum is rounded as it is written.
 #pragma clang fp contract(off)
 
@@ -249,40 +250,19 @@ extern "C" int swf_dd_select_batch(int32_t n_windows, const int32_t* epoch_first
     if (chk) return chk;
 
     const size_t nw = (size_t)n_windows, ne = (size_t)epoch_first[n_windows], no = (size_t)obs_first[ne], ny = (size_t)y_first[n_windows];
-    const size_t ne1 = std::max<size_t>(ne, 1), no1 = std::max<size_t>(no, 1), ny1 = std::max<size_t>(ny, 1);
-    std::vector<void*> bufs;
-    auto cleanup = [&]() { for (void* p : bufs) (void)hipFree(p); };
-#define DDS_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return dds_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    auto dev = [&](size_t bytes, const void* src, size_t src_bytes, void** out) -> hipError_t {
-        hipError_t rc = hipMalloc(out, bytes);
-        if (rc != hipSuccess) return rc;
-        bufs.push_back(*out);
-        return src_bytes ? hipMemcpyAsync(*out, src, src_bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
-    void *d_ef, *d_of, *d_obs, *d_yf, *d_y, *d_gate, *d_pairs, *d_counts, *d_refs, *d_cost, *d_role;
-    DDS_TRY(dev((nw + 1) * sizeof(int), epoch_first, (nw + 1) * sizeof(int), &d_ef));
-    DDS_TRY(dev((ne + 1) * sizeof(int), obs_first, (ne + 1) * sizeof(int), &d_of));
-    DDS_TRY(dev(no1 * 2 * sizeof(int), obs, no * 2 * sizeof(int), &d_obs));
-    DDS_TRY(dev((nw + 1) * sizeof(int), y_first, (nw + 1) * sizeof(int), &d_yf));
-    DDS_TRY(dev(ny1 * sizeof(double), y, ny * sizeof(double), &d_y));
-    DDS_TRY(dev(nw * sizeof(double), gate, nw * sizeof(double), &d_gate));
-    DDS_TRY(dev(nw * SWF_LAMBDA_NMAX * 2 * sizeof(int), nullptr, 0, &d_pairs));
-    DDS_TRY(dev(nw * 4 * sizeof(int), nullptr, 0, &d_counts));
-    DDS_TRY(dev(ne1 * DDS_CLASSES * sizeof(int), nullptr, 0, &d_refs));
-    DDS_TRY(dev(no1 * sizeof(double), nullptr, 0, &d_cost));
-    DDS_TRY(dev(no1, nullptr, 0, &d_role));
-    A.epoch_first = (const int*)d_ef; A.obs_first = (const int*)d_of; A.obs = (const int*)d_obs; A.y_first = (const int*)d_yf;
-    A.y = (const double*)d_y; A.gate = (const double*)d_gate;
-    A.pairs = (int*)d_pairs; A.counts = (int*)d_counts; A.refs = (int*)d_refs; A.cost = (double*)d_cost; A.role = (unsigned char*)d_role;
+    HostStage S(who, st);
+    A.epoch_first = S.up(epoch_first, nw + 1); A.obs_first = S.up(obs_first, ne + 1); A.obs = S.up(obs, no * 2, 2);
+    A.y_first = S.up(y_first, nw + 1); A.y = S.up(y, ny, 1); A.gate = S.up(gate, nw);
+    A.pairs = S.out<int32_t>(nw * SWF_LAMBDA_NMAX * 2); A.counts = S.out<int32_t>(nw * 4); A.refs = S.out<int32_t>(ne * DDS_CLASSES, DDS_CLASSES);
+    A.cost = S.out<double>(no); A.role = S.out<uint8_t>(no);
+    if (S.failed()) return S.rc();
     const int rc = swf_internal_dd_select_launch(A, false, st);
-    if (rc) { cleanup(); return rc; }
-    if (pairs) DDS_TRY(hipMemcpyAsync(pairs, d_pairs, nw * SWF_LAMBDA_NMAX * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (counts) DDS_TRY(hipMemcpyAsync(counts, d_counts, nw * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (refs && ne) DDS_TRY(hipMemcpyAsync(refs, d_refs, ne * DDS_CLASSES * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (cost && no) DDS_TRY(hipMemcpyAsync(cost, d_cost, no * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (role && no) DDS_TRY(hipMemcpyAsync(role, d_role, no, hipMemcpyDeviceToHost, st));
-    DDS_TRY(hipStreamSynchronize(st));
-#undef DDS_TRY
-    cleanup();
-    return SWF_OK;
+    if (rc) return rc;
+    S.down(pairs, A.pairs, nw * SWF_LAMBDA_NMAX * 2);
+    S.down(counts, A.counts, nw * 4);
+    S.down(refs, A.refs, ne * DDS_CLASSES);
+    S.down(cost, A.cost, no);
+    S.down(role, A.role, no);
+    S.sync();
+    return S.rc();
 }

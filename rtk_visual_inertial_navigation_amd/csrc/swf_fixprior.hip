@@ -8,6 +8,7 @@
 #include "swf_fixprior.h"
 #include "swf_lambda.h"
 #include "swf_rootdev.h"
+#include "swf_stage.h"
 
 void swf_internal_set_error(const std::string& m);
 static int fxp_fail(int code, const std::string& m) { swf_internal_set_error(m); return code; }
@@ -358,46 +359,22 @@ extern "C" int swf_prior_fix_batch(int32_t n, const int32_t* dim, const double* 
         if (rc) return rc;
         t1 += (size_t)dim[p]; t2 += (size_t)dim[p] * dim[p];
     }
-    const size_t np = (size_t)n, nrw = (size_t)std::max(row_first[n], 1);
-    int *d_dim = nullptr, *d_first = nullptr, *d_rows = nullptr, *d_rank = nullptr;
-    double *d_J = nullptr, *d_r = nullptr, *d_vals = nullptr, *d_A = nullptr, *d_b = nullptr, *d_Jn = nullptr, *d_r0 = nullptr, *d_eig = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(d_dim); (void)hipFree(d_first); (void)hipFree(d_rows); (void)hipFree(d_rank); (void)hipFree(d_J); (void)hipFree(d_r);
-        (void)hipFree(d_vals); (void)hipFree(d_A); (void)hipFree(d_b); (void)hipFree(d_Jn); (void)hipFree(d_r0); (void)hipFree(d_eig);
-    };
-#define FXP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fxp_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    FXP_TRY(hipMalloc(&d_dim, np * sizeof(int)));
-    FXP_TRY(hipMalloc(&d_first, (np + 1) * sizeof(int)));
-    FXP_TRY(hipMalloc(&d_rows, nrw * 2 * sizeof(int)));
-    FXP_TRY(hipMalloc(&d_rank, np * sizeof(int)));
-    FXP_TRY(hipMalloc(&d_J, t2 * sizeof(double)));
-    FXP_TRY(hipMalloc(&d_r, t1 * sizeof(double)));
-    FXP_TRY(hipMalloc(&d_vals, nrw * sizeof(double)));
-    FXP_TRY(hipMalloc(&d_A, t2 * sizeof(double)));
-    FXP_TRY(hipMalloc(&d_b, t1 * sizeof(double)));
-    FXP_TRY(hipMalloc(&d_Jn, t2 * sizeof(double)));
-    FXP_TRY(hipMalloc(&d_r0, t1 * sizeof(double)));
-    FXP_TRY(hipMalloc(&d_eig, t1 * sizeof(double)));
-    FXP_TRY(hipMemcpyAsync(d_dim, dim, np * sizeof(int), hipMemcpyHostToDevice, st));
-    FXP_TRY(hipMemcpyAsync(d_first, row_first, (np + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    if (row_first[n] > 0) {
-        FXP_TRY(hipMemcpyAsync(d_rows, rows, (size_t)row_first[n] * 2 * sizeof(int), hipMemcpyHostToDevice, st));
-        FXP_TRY(hipMemcpyAsync(d_vals, vals, (size_t)row_first[n] * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    FXP_TRY(hipMemcpyAsync(d_J, J, t2 * sizeof(double), hipMemcpyHostToDevice, st));
-    FXP_TRY(hipMemcpyAsync(d_r, r, t1 * sizeof(double), hipMemcpyHostToDevice, st));
-    P.dim = d_dim; P.J = d_J; P.r = d_r; P.row_first = d_first; P.rows = d_rows; P.vals = d_vals;
-    P.A = d_A; P.b = d_b; P.Jn = d_Jn; P.r0 = d_r0; P.eig = d_eig; P.rank = d_rank;
+    const size_t np = (size_t)n, nrw = (size_t)row_first[n];
+    HostStage S(who, st);
+    P.dim = S.up(dim, np); P.row_first = S.up(row_first, np + 1);
+    P.rows = S.up(rows, nrw * 2, 2); P.vals = S.up(vals, nrw, 1);
+    P.J = S.up(J, t2); P.r = S.up(r, t1);
+    P.A = S.out<double>(t2); P.b = S.out<double>(t1); P.Jn = S.out<double>(t2); P.r0 = S.out<double>(t1); P.eig = S.out<double>(t1);
+    P.rank = S.out<int32_t>(np);
+    if (S.failed()) return S.rc();
     const int rc = swf_internal_fix_prior_launch(P, DevBatch{}, false, st);
-    if (rc) { cleanup(); return rc; }
-    if (A) FXP_TRY(hipMemcpyAsync(A, d_A, t2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (b) FXP_TRY(hipMemcpyAsync(b, d_b, t1 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (Jn) FXP_TRY(hipMemcpyAsync(Jn, d_Jn, t2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (r0) FXP_TRY(hipMemcpyAsync(r0, d_r0, t1 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (eig) FXP_TRY(hipMemcpyAsync(eig, d_eig, t1 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (rank) FXP_TRY(hipMemcpyAsync(rank, d_rank, np * sizeof(int), hipMemcpyDeviceToHost, st));
-    FXP_TRY(hipStreamSynchronize(st));
-#undef FXP_TRY
-    cleanup();
-    return SWF_OK;
+    if (rc) return rc;
+    S.down(A, P.A, t2);
+    S.down(b, P.b, t1);
+    S.down(Jn, P.Jn, t2);
+    S.down(r0, P.r0, t1);
+    S.down(eig, P.eig, t1);
+    S.down(rank, P.rank, np);
+    S.sync();
+    return S.rc();
 }

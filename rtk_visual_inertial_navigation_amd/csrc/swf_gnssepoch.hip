@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 #include "swf_gnssepoch.h"
+#include "swf_devutil.h"
+#include "swf_stage.h"
 // Floating-point contraction is off in this translation unit, gnss_distance and gnss_range_rate included: every product and sum is
 // rounded as it is written, so the two instances of the kernel cannot differ in where a multiply-add was fused.
 #pragma clang fp contract(off)
@@ -24,8 +26,6 @@ __device__ __forceinline__ double ges_lane(double v, int k) {       // the value
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), k);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
-
-__device__ __forceinline__ bool ges_finite(double v) { return fabs(v) < __builtin_inf(); }          // false for a NaN
 
 // Sums q[k] over the wavefront for every k at once.  Halving steps over lane bits 32, 16, ...: a lane whose bit is set keeps the
 // upper half of its quantities and hands the lower half to its partner, the partner the reverse; after log2 K steps a lane holds one
@@ -80,7 +80,7 @@ __device__ __forceinline__ bool ges_bad(const GesRec& R) {
     bool bad = R.kind < 0 || R.kind > SWF_GES_DOPPLER || R.slot < 0 || R.slot >= SWF_GES_CLOCKS || (R.st & ~SWF_GES_AMB_FREE) != 0 || R.pad != 0;
     bad |= (R.st & SWF_GES_AMB_FREE) != 0 && !phase;
 #pragma unroll
-    for (int k = 0; k < SWF_GES_DOUBLES; k++) bad |= !ges_finite(R.d[k]);
+    for (int k = 0; k < SWF_GES_DOUBLES; k++) bad |= !swf_finite(R.d[k]);
     bad |= !(R.d[GES_D_W] >= 0.0);
     bad |= phase && !(R.d[GES_D_LAM] > 0.0);
     return bad;
@@ -162,9 +162,9 @@ __global__ void __launch_bounds__(64 * GES_WPB) k_gnss_epoch(GnssEpochArgs A) {
     const int mode = A.mode[e], cc = A.clk_const[e];
 
     // ---------------------------------------------------------------- what the host rejects; the determining rows of every clock
-    bool bad = !ges_finite(clk0) || (mode & ~(SWF_GES_FREE_POS | SWF_GES_FREE_VEL)) != 0 || (cc & ~((1 << SWF_GES_CLOCKS) - 1)) != 0;
+    bool bad = !swf_finite(clk0) || (mode & ~(SWF_GES_FREE_POS | SWF_GES_FREE_VEL)) != 0 || (cc & ~((1 << SWF_GES_CLOCKS) - 1)) != 0;
 #pragma unroll
-    for (int k = 0; k < 3; k++) bad |= !ges_finite(pos0[k]) || !ges_finite(vel0[k]) || !ges_finite(base[k]);
+    for (int k = 0; k < 3; k++) bad |= !swf_finite(pos0[k]) || !swf_finite(vel0[k]) || !swf_finite(base[k]);
     int rows = 0;                                                        // lane s: rows without AMB_FREE, w > 0, on clock s
     for (int c = 0; c < nch; c++) {
         if (!RES) ges_load(A, f0, n, c * 64 + lane, R);
@@ -440,56 +440,27 @@ extern "C" int swf_gnss_epoch_solve_batch(int32_t n_epochs, const int32_t* first
     }
     if (nmax > SWF_GES_NMAX) return ges_fail(SWF_E_UNSUPPORTED, std::string(who) + ": more than 512 records in an epoch");
 
-    const size_t ne = (size_t)n_epochs, nr = (size_t)first[n_epochs], nr1 = std::max<size_t>(nr, 1);
-    std::vector<void*> bufs;
-    auto cleanup = [&]() { for (void* p : bufs) (void)hipFree(p); };
-#define GES_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return ges_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    auto dev = [&](size_t bytes, const void* src, void** out) -> hipError_t {
-        hipError_t rc = hipMalloc(out, bytes);
-        if (rc != hipSuccess) return rc;
-        bufs.push_back(*out);
-        return src ? hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
-    const size_t D = sizeof(double), I = sizeof(int);
-    void *d_first, *d_pos, *d_vel, *d_base, *d_clock, *d_mode, *d_cc, *d_dat, *d_rec;
-    void *o_pos, *o_vel, *o_clock, *o_N, *o_r, *o_cost, *o_it, *o_st, *o_rows, *o_info;
-    GES_TRY(dev((ne + 1) * I, first, &d_first));
-    GES_TRY(dev(ne * 3 * D, pos, &d_pos));
-    GES_TRY(dev(ne * 3 * D, vel, &d_vel));
-    GES_TRY(dev(ne * 3 * D, base, &d_base));
-    GES_TRY(dev(ne * SWF_GES_CLOCKS * D, clock, &d_clock));
-    GES_TRY(dev(ne * I, mode, &d_mode));
-    GES_TRY(dev(ne * I, clk_const, &d_cc));
-    GES_TRY(dev(nr1 * SWF_GES_DOUBLES * D, nr ? dat : nullptr, &d_dat));
-    GES_TRY(dev(nr1 * 4 * I, nr ? rec : nullptr, &d_rec));
-    GES_TRY(dev(ne * 3 * D, nullptr, &o_pos));
-    GES_TRY(dev(ne * 3 * D, nullptr, &o_vel));
-    GES_TRY(dev(ne * SWF_GES_CLOCKS * D, nullptr, &o_clock));
-    GES_TRY(dev(nr1 * D, nullptr, &o_N));
-    GES_TRY(dev(nr1 * D, nullptr, &o_r));
-    GES_TRY(dev(ne * D, nullptr, &o_cost));
-    GES_TRY(dev(ne * I, nullptr, &o_it));
-    GES_TRY(dev(ne * I, nullptr, &o_st));
-    GES_TRY(dev(ne * SWF_GES_CLOCKS * I, nullptr, &o_rows));
-    GES_TRY(dev(ne * 36 * D, nullptr, &o_info));
-    A.first = (const int*)d_first; A.pos = (const double*)d_pos; A.vel = (const double*)d_vel; A.base = (const double*)d_base;
-    A.clock = (const double*)d_clock; A.mode = (const int*)d_mode; A.clk_const = (const int*)d_cc; A.dat = (const double*)d_dat; A.rec = (const int*)d_rec;
-    A.pos_out = (double*)o_pos; A.vel_out = (double*)o_vel; A.clock_out = (double*)o_clock; A.N_out = (double*)o_N; A.r_out = (double*)o_r;
-    A.cost = (double*)o_cost; A.iters = (int*)o_it; A.status = (int*)o_st; A.clk_rows = (int*)o_rows; A.info = (double*)o_info;
+    const size_t ne = (size_t)n_epochs, nr = (size_t)first[n_epochs];
+    HostStage S(who, st);
+    A.first = S.up(first, ne + 1); A.pos = S.up(pos, ne * 3); A.vel = S.up(vel, ne * 3); A.base = S.up(base, ne * 3);
+    A.clock = S.up(clock, ne * SWF_GES_CLOCKS); A.mode = S.up(mode, ne); A.clk_const = S.up(clk_const, ne);
+    A.dat = S.up(dat, nr * SWF_GES_DOUBLES, SWF_GES_DOUBLES); A.rec = S.up(rec, nr * 4, 4);
+    A.pos_out = S.out<double>(ne * 3); A.vel_out = S.out<double>(ne * 3); A.clock_out = S.out<double>(ne * SWF_GES_CLOCKS);
+    A.N_out = S.out<double>(nr); A.r_out = S.out<double>(nr); A.cost = S.out<double>(ne);
+    A.iters = S.out<int32_t>(ne); A.status = S.out<int32_t>(ne); A.clk_rows = S.out<int32_t>(ne * SWF_GES_CLOCKS); A.info = S.out<double>(ne * 36);
+    if (S.failed()) return S.rc();
     const int rc = swf_internal_gnss_epoch_launch(A, nmax <= 64, st);
-    if (rc) { cleanup(); return rc; }
-    if (pos_out) GES_TRY(hipMemcpyAsync(pos_out, o_pos, ne * 3 * D, hipMemcpyDeviceToHost, st));
-    if (vel_out) GES_TRY(hipMemcpyAsync(vel_out, o_vel, ne * 3 * D, hipMemcpyDeviceToHost, st));
-    if (clock_out) GES_TRY(hipMemcpyAsync(clock_out, o_clock, ne * SWF_GES_CLOCKS * D, hipMemcpyDeviceToHost, st));
-    if (N_out && nr) GES_TRY(hipMemcpyAsync(N_out, o_N, nr * D, hipMemcpyDeviceToHost, st));
-    if (r_out && nr) GES_TRY(hipMemcpyAsync(r_out, o_r, nr * D, hipMemcpyDeviceToHost, st));
-    if (cost) GES_TRY(hipMemcpyAsync(cost, o_cost, ne * D, hipMemcpyDeviceToHost, st));
-    if (iters) GES_TRY(hipMemcpyAsync(iters, o_it, ne * I, hipMemcpyDeviceToHost, st));
-    if (status) GES_TRY(hipMemcpyAsync(status, o_st, ne * I, hipMemcpyDeviceToHost, st));
-    if (clk_rows) GES_TRY(hipMemcpyAsync(clk_rows, o_rows, ne * SWF_GES_CLOCKS * I, hipMemcpyDeviceToHost, st));
-    if (info) GES_TRY(hipMemcpyAsync(info, o_info, ne * 36 * D, hipMemcpyDeviceToHost, st));
-    GES_TRY(hipStreamSynchronize(st));
-#undef GES_TRY
-    cleanup();
-    return SWF_OK;
+    if (rc) return rc;
+    S.down(pos_out, A.pos_out, ne * 3);
+    S.down(vel_out, A.vel_out, ne * 3);
+    S.down(clock_out, A.clock_out, ne * SWF_GES_CLOCKS);
+    S.down(N_out, A.N_out, nr);
+    S.down(r_out, A.r_out, nr);
+    S.down(cost, A.cost, ne);
+    S.down(iters, A.iters, ne);
+    S.down(status, A.status, ne);
+    S.down(clk_rows, A.clk_rows, ne * SWF_GES_CLOCKS);
+    S.down(info, A.info, ne * 36);
+    S.sync();
+    return S.rc();
 }

@@ -7,6 +7,7 @@
 #include <vector>
 #define SWF_LAMBDA_DEVICE_BODY
 #include "swf_lambda.h"
+#include "swf_stage.h"
 
 void swf_internal_set_error(const std::string& m);
 static int lbd_fail(int code, const std::string& m) { swf_internal_set_error(m); return code; }
@@ -51,28 +52,17 @@ extern "C" int swf_lambda_batch(int32_t n_problems, int32_t ld, const int32_t* n
     }
     A.ldl = lbd_ldl(nmax);
     const size_t np = (size_t)n_problems;
-    int* d_n = nullptr; int* d_info = nullptr; double *d_a = nullptr, *d_Q = nullptr, *d_F = nullptr, *d_s = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_n); (void)hipFree(d_info); (void)hipFree(d_a); (void)hipFree(d_Q); (void)hipFree(d_F); (void)hipFree(d_s); };
-#define LBD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return lbd_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    LBD_TRY(hipMalloc(&d_n, np * sizeof(int)));
-    LBD_TRY(hipMalloc(&d_info, np * sizeof(int)));
-    LBD_TRY(hipMalloc(&d_a, np * ld * sizeof(double)));
-    LBD_TRY(hipMalloc(&d_Q, np * ld * ld * sizeof(double)));
-    LBD_TRY(hipMalloc(&d_F, np * m * ld * sizeof(double)));
-    LBD_TRY(hipMalloc(&d_s, np * m * sizeof(double)));
-    LBD_TRY(hipMemcpyAsync(d_n, n, np * sizeof(int), hipMemcpyHostToDevice, st));
-    LBD_TRY(hipMemcpyAsync(d_a, a, np * ld * sizeof(double), hipMemcpyHostToDevice, st));
-    LBD_TRY(hipMemcpyAsync(d_Q, Q, np * ld * ld * sizeof(double), hipMemcpyHostToDevice, st));
-    A.n = d_n; A.a = d_a; A.Q = d_Q; A.F = d_F; A.s = d_s; A.info = d_info;
+    HostStage S("swf_lambda_batch", st);
+    A.n = S.up(n, np); A.a = S.up(a, np * ld); A.Q = S.up(Q, np * ld * ld);
+    A.F = S.out<double>(np * m * ld); A.s = S.out<double>(np * m); A.info = S.out<int32_t>(np);
+    if (S.failed()) return S.rc();
     const int rc = swf_internal_lambda_launch(A, false, st);
-    if (rc) { cleanup(); return rc; }
-    LBD_TRY(hipMemcpyAsync(F, d_F, np * m * ld * sizeof(double), hipMemcpyDeviceToHost, st));
-    LBD_TRY(hipMemcpyAsync(s, d_s, np * m * sizeof(double), hipMemcpyDeviceToHost, st));
-    LBD_TRY(hipMemcpyAsync(info, d_info, np * sizeof(int), hipMemcpyDeviceToHost, st));
-    LBD_TRY(hipStreamSynchronize(st));
-#undef LBD_TRY
-    cleanup();
-    return SWF_OK;
+    if (rc) return rc;
+    S.down(F, A.F, np * m * ld);
+    S.down(s, A.s, np * m);
+    S.down(info, A.info, np);
+    S.sync();
+    return S.rc();
 }
 
 #ifdef SWF_PROFILE_LAMBDA

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "swf_phasescreen.h"
+#include "swf_stage.h"
 // Floating-point contraction is off in this translation unit, gnss_distance included: every product and sum is rounded as it is
 // written, so the two instances of the kernel cannot differ in where a multiply-add was fused.
 #pragma clang fp contract(off)
@@ -271,42 +272,21 @@ extern "C" int swf_phase_screen_batch(int32_t n_epochs, const int32_t* first, co
     }
     if (nmax > SWF_SCR_NMAX) return scr_fail(SWF_E_UNSUPPORTED, std::string(who) + ": more than 256 records in an epoch");
 
-    const size_t ne = (size_t)n_epochs, nr = (size_t)first[n_epochs], nr1 = std::max<size_t>(nr, 1);
-    std::vector<void*> bufs;
-    auto cleanup = [&]() { for (void* p : bufs) (void)hipFree(p); };
-#define SCR_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return scr_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    auto dev = [&](size_t bytes, const void* src, void** out) -> hipError_t {
-        hipError_t rc = hipMalloc(out, bytes);
-        if (rc != hipSuccess) return rc;
-        bufs.push_back(*out);
-        return src ? hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
-    void *d_first, *d_pos, *d_base, *d_mode, *d_dat, *d_rec, *d_r, *d_fl, *d_med, *d_cnt, *d_reset, *d_nreset;
-    SCR_TRY(dev((ne + 1) * sizeof(int), first, &d_first));
-    SCR_TRY(dev(ne * 3 * sizeof(double), pos, &d_pos));
-    SCR_TRY(dev(ne * 3 * sizeof(double), base, &d_base));
-    SCR_TRY(dev(ne * sizeof(int), mode, &d_mode));
-    SCR_TRY(dev(nr1 * SWF_SCR_DOUBLES * sizeof(double), nr ? dat : nullptr, &d_dat));
-    SCR_TRY(dev(nr1 * 4 * sizeof(int), nr ? rec : nullptr, &d_rec));
-    SCR_TRY(dev(nr1 * sizeof(double), nullptr, &d_r));
-    SCR_TRY(dev(nr1, nullptr, &d_fl));
-    SCR_TRY(dev(ne * SCR_SETS * sizeof(double), nullptr, &d_med));
-    SCR_TRY(dev(ne * SCR_SETS * sizeof(int), nullptr, &d_cnt));
-    SCR_TRY(dev(nr1 * sizeof(int), nullptr, &d_reset));
-    SCR_TRY(dev(ne * sizeof(int), nullptr, &d_nreset));
-    A.first = (const int*)d_first; A.pos = (const double*)d_pos; A.base = (const double*)d_base; A.mode = (const int*)d_mode;
-    A.dat = (const double*)d_dat; A.rec = (const int*)d_rec;
-    A.r = (double*)d_r; A.flags = (unsigned char*)d_fl; A.med = (double*)d_med; A.cnt = (int*)d_cnt; A.reset = (int*)d_reset; A.n_reset = (int*)d_nreset;
+    const size_t ne = (size_t)n_epochs, nr = (size_t)first[n_epochs];
+    HostStage S(who, st);
+    A.first = S.up(first, ne + 1); A.pos = S.up(pos, ne * 3); A.base = S.up(base, ne * 3); A.mode = S.up(mode, ne);
+    A.dat = S.up(dat, nr * SWF_SCR_DOUBLES, SWF_SCR_DOUBLES); A.rec = S.up(rec, nr * 4, 4);
+    A.r = S.out<double>(nr); A.flags = S.out<uint8_t>(nr); A.med = S.out<double>(ne * SCR_SETS); A.cnt = S.out<int32_t>(ne * SCR_SETS);
+    A.reset = S.out<int32_t>(nr); A.n_reset = S.out<int32_t>(ne);
+    if (S.failed()) return S.rc();
     const int rc = swf_internal_phase_screen_launch(A, nmax <= 64 ? 1 : SWF_SCR_NMAX / 64, st);
-    if (rc) { cleanup(); return rc; }
-    if (r && nr) SCR_TRY(hipMemcpyAsync(r, d_r, nr * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (flags && nr) SCR_TRY(hipMemcpyAsync(flags, d_fl, nr, hipMemcpyDeviceToHost, st));
-    if (med) SCR_TRY(hipMemcpyAsync(med, d_med, ne * SCR_SETS * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (cnt) SCR_TRY(hipMemcpyAsync(cnt, d_cnt, ne * SCR_SETS * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (reset && nr) SCR_TRY(hipMemcpyAsync(reset, d_reset, nr * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (n_reset) SCR_TRY(hipMemcpyAsync(n_reset, d_nreset, ne * sizeof(int), hipMemcpyDeviceToHost, st));
-    SCR_TRY(hipStreamSynchronize(st));
-#undef SCR_TRY
-    cleanup();
-    return SWF_OK;
+    if (rc) return rc;
+    S.down(r, A.r, nr);
+    S.down(flags, A.flags, nr);
+    S.down(med, A.med, ne * SCR_SETS);
+    S.down(cnt, A.cnt, ne * SCR_SETS);
+    S.down(reset, A.reset, nr);
+    S.down(n_reset, A.n_reset, ne);
+    S.sync();
+    return S.rc();
 }

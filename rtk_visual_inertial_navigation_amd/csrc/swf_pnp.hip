@@ -6,20 +6,13 @@
 #include <string>
 #include <vector>
 #include "swf_pnp.h"
+#include "swf_devutil.h"
+#include "swf_stage.h"
 
 void swf_internal_set_error(const std::string& m);
 static int pnp_fail(int code, const std::string& m) { swf_internal_set_error(m); return code; }
 
 namespace {
-
-__device__ __forceinline__ unsigned long long pnp_mix(unsigned long long x) {     // splitmix64's output at state x + 0x9E37..
-    unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ bool pnp_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 // The inlier test.  Every operation is written out (no contraction left to the compiler), so the count of the scoring loop and the
 // mask written later from the best hypothesis are the same decisions.
@@ -93,7 +86,7 @@ __device__ __forceinline__ bool pnp_solve(const double acc[27], double x[6]) {
         x[i] = s / L[i * (i + 1) / 2 + i];
     }
 #pragma unroll
-    for (int i = 0; i < 6; i++) ok = ok && pnp_finite(x[i]);
+    for (int i = 0; i < 6; i++) ok = ok && swf_finite(x[i]);
     return ok;
 }
 
@@ -122,20 +115,6 @@ __device__ __forceinline__ void pnp_update(double R[9], double t[3], const doubl
     t[0] += x[3]; t[1] += x[4]; t[2] += x[5];
 }
 
-// OpenCV's RANSACUpdateNumIters with ep = (n - count) / n; the power is m - 1 products
-__device__ __forceinline__ int pnp_update_iters(double conf, int count, int n, int m, int n_iters) {
-    const double p = fmin(fmax(conf, 0.0), 1.0);
-    const double ep = fmin(fmax((double)(n - count) / (double)n, 0.0), 1.0);
-    const double num = fmax(1.0 - p, DBL_MIN), w = 1.0 - ep;
-    double wm = w;
-    for (int i = 1; i < m; i++) wm *= w;
-    const double d = 1.0 - wm;
-    if (d < DBL_MIN) return 0;
-    const double ln = log(num), ld = log(d);
-    if (ld >= 0.0 || -ln >= (double)n_iters * -ld) return n_iters;
-    return (int)rint(ln / ld);
-}
-
 __global__ void __launch_bounds__(PNP_THREADS) k_pnp_frame(PnpArgs A) {
     __shared__ double s_p[5 * PNP_NMAX];                // X | Y | Z | u | v, each PNP_NMAX long
     __shared__ double s_red[9 * PNP_THREADS];
@@ -161,15 +140,15 @@ __global__ void __launch_bounds__(PNP_THREADS) k_pnp_frame(PnpArgs A) {
 #pragma unroll
         for (int k = 0; k < 5; k++) {
             if (A.flags & 1) c[k] = (double)(float)c[k];
-            bad |= !pnp_finite(c[k]);
+            bad |= !swf_finite(c[k]);
             s_p[k * PNP_NMAX + i] = c[k];
         }
     }
     double Pp[3], Rp[9];
 #pragma unroll
-    for (int k = 0; k < 3; k++) { Pp[k] = A.Ps_prev[(size_t)f * 3 + k]; bad |= !pnp_finite(Pp[k]); }
+    for (int k = 0; k < 3; k++) { Pp[k] = A.Ps_prev[(size_t)f * 3 + k]; bad |= !swf_finite(Pp[k]); }
 #pragma unroll
-    for (int k = 0; k < 9; k++) { Rp[k] = A.Rs_prev[(size_t)f * 9 + k]; bad |= !pnp_finite(Rp[k]); }
+    for (int k = 0; k < 9; k++) { Rp[k] = A.Rs_prev[(size_t)f * 9 + k]; bad |= !swf_finite(Rp[k]); }
     if (tid == 0) s_scan[3] = 0;
     __syncthreads();
     if (bad) s_scan[3] = 1;
@@ -205,7 +184,7 @@ __global__ void __launch_bounds__(PNP_THREADS) k_pnp_frame(PnpArgs A) {
         int got = 0;
         if (n == 4) { smp[0] = 0; smp[1] = 1; smp[2] = 2; smp[3] = 3; got = 4; }
         else for (int j = 0; j < PNP_DRAWS && got < 5; j++) {
-            const unsigned long long x = pnp_mix(A.seed + 64ull * (unsigned long long)tid + (unsigned long long)j);
+            const unsigned long long x = swf_mix(A.seed + 64ull * (unsigned long long)tid + (unsigned long long)j);
             const int idx = (int)(((x >> 32) * (unsigned long long)n) >> 32);
             bool dup = false;
 #pragma unroll
@@ -232,9 +211,9 @@ __global__ void __launch_bounds__(PNP_THREADS) k_pnp_frame(PnpArgs A) {
         }
         if (valid) {
 #pragma unroll
-            for (int i = 0; i < 9; i++) valid = valid && pnp_finite(R[i]);
+            for (int i = 0; i < 9; i++) valid = valid && swf_finite(R[i]);
 #pragma unroll
-            for (int i = 0; i < 3; i++) valid = valid && pnp_finite(t[i]);
+            for (int i = 0; i < 3; i++) valid = valid && swf_finite(t[i]);
         }
         if (valid) for (int i = 0; i < n; i++)
             cnt += pnp_inlier(R, t, s_p[i], s_p[PNP_NMAX + i], s_p[2 * PNP_NMAX + i], s_p[3 * PNP_NMAX + i], s_p[4 * PNP_NMAX + i], A.thr2) ? 1 : 0;
@@ -248,7 +227,7 @@ __global__ void __launch_bounds__(PNP_THREADS) k_pnp_frame(PnpArgs A) {
             const int c = s_count[k];
             if (c > max(best_count, m - 1)) {
                 best = k; best_count = c;
-                n_iters = pnp_update_iters(A.confidence, c, n, m, n_iters);
+                n_iters = swf_update_iters(A.confidence, c, n, m, n_iters);
             }
         }
         s_scan[0] = best; s_scan[1] = n_iters; s_scan[2] = best_count; s_scan[3] = 0;
@@ -323,9 +302,9 @@ __global__ void __launch_bounds__(PNP_THREADS) k_pnp_frame(PnpArgs A) {
     }
     if (refined) {
 #pragma unroll
-        for (int i = 0; i < 9; i++) refined = refined && pnp_finite(R[i]);
+        for (int i = 0; i < 9; i++) refined = refined && swf_finite(R[i]);
 #pragma unroll
-        for (int i = 0; i < 3; i++) refined = refined && pnp_finite(t[i]);
+        for (int i = 0; i < 3; i++) refined = refined && swf_finite(t[i]);
     }
     if (!refined) {
 #pragma unroll
@@ -423,53 +402,41 @@ extern "C" int swf_pnp_frame_batch(int32_t n_frames, const int32_t* first, const
     const size_t nf = (size_t)n_frames, np = (size_t)(first[n_frames] - first[0]), H = (size_t)iterations;
     std::vector<int32_t> rel(first, first + n_frames + 1);
     for (auto& v : rel) v -= first[0];
-    std::vector<void*> bufs;
-    auto cleanup = [&]() { for (void* p : bufs) (void)hipFree(p); };
-#define PNP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return pnp_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    auto dev = [&](size_t bytes, const void* src, void** out) -> hipError_t {
-        hipError_t rc = hipMalloc(out, std::max<size_t>(bytes, 8));
-        if (rc != hipSuccess) return rc;
-        bufs.push_back(*out);
-        return src && bytes ? hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
-    void *d_f, *d_w, *d_uv, *d_pp, *d_rp, *d_po, *d_ro, *d_ni, *d_in, *d_b, *d_it, *d_info, *d_s = nullptr, *d_h = nullptr, *d_c = nullptr;
-    PNP_TRY(dev(rel.size() * sizeof(int32_t), rel.data(), &d_f));
-    PNP_TRY(dev(np * 3 * sizeof(double), pts_w + (size_t)first[0] * 3, &d_w));
-    PNP_TRY(dev(np * 2 * sizeof(double), pts_uv + (size_t)first[0] * 2, &d_uv));
-    PNP_TRY(dev(nf * 3 * sizeof(double), Ps_prev, &d_pp));
-    PNP_TRY(dev(nf * 9 * sizeof(double), Rs_prev, &d_rp));
-    PNP_TRY(dev(nf * 3 * sizeof(double), nullptr, &d_po));
-    PNP_TRY(dev(nf * 9 * sizeof(double), nullptr, &d_ro));
-    PNP_TRY(dev(nf * sizeof(int32_t), nullptr, &d_ni));
-    PNP_TRY(dev(np, nullptr, &d_in));
-    PNP_TRY(dev(nf * sizeof(int32_t), nullptr, &d_b));
-    PNP_TRY(dev(nf * sizeof(int32_t), nullptr, &d_it));
-    PNP_TRY(dev(nf * sizeof(int32_t), nullptr, &d_info));
-    if (samples) PNP_TRY(dev(nf * H * 5 * sizeof(int32_t), nullptr, &d_s));
-    if (hyp) PNP_TRY(dev(nf * H * 12 * sizeof(double), nullptr, &d_h));
-    if (count) PNP_TRY(dev(nf * H * sizeof(int32_t), nullptr, &d_c));
-    A.first = (const int*)d_f; A.pts_w = (const double*)d_w; A.pts_uv = (const double*)d_uv; A.Ps_prev = (const double*)d_pp; A.Rs_prev = (const double*)d_rp;
-    A.Ps_out = (double*)d_po; A.Rs_out = (double*)d_ro; A.n_inliers = (int*)d_ni; A.inlier = (unsigned char*)d_in; A.best = (int*)d_b;
-    A.n_iters = (int*)d_it; A.info = (int*)d_info; A.samples = (int*)d_s; A.hyp = (double*)d_h; A.count = (int*)d_c;
-    const int rc = swf_internal_pnp_launch(A, st);
-    if (rc) { cleanup(); return rc; }
     // a frame without a model leaves the caller's arrays as they are: the results pass through staging arrays
     std::vector<double> h_po(nf * 3), h_ro(nf * 9), h_h(hyp ? nf * H * 12 : 0);
     std::vector<int32_t> h_ni(nf), h_b(nf), h_it(nf), h_info(nf), h_s(samples ? nf * H * 5 : 0), h_c(count ? nf * H : 0);
-    std::vector<uint8_t> h_in(std::max<size_t>(np, 1));
-    PNP_TRY(hipMemcpyAsync(h_po.data(), d_po, h_po.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PNP_TRY(hipMemcpyAsync(h_ro.data(), d_ro, h_ro.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PNP_TRY(hipMemcpyAsync(h_ni.data(), d_ni, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (np) PNP_TRY(hipMemcpyAsync(h_in.data(), d_in, np, hipMemcpyDeviceToHost, st));
-    PNP_TRY(hipMemcpyAsync(h_b.data(), d_b, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PNP_TRY(hipMemcpyAsync(h_it.data(), d_it, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PNP_TRY(hipMemcpyAsync(h_info.data(), d_info, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (samples) PNP_TRY(hipMemcpyAsync(h_s.data(), d_s, h_s.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (hyp) PNP_TRY(hipMemcpyAsync(h_h.data(), d_h, h_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (count) PNP_TRY(hipMemcpyAsync(h_c.data(), d_c, h_c.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PNP_TRY(hipStreamSynchronize(st));
-#undef PNP_TRY
-    cleanup();
+    std::vector<uint8_t> h_in(np);
+    HostStage S("swf_pnp_frame_batch", st);
+    A.first = S.up(rel.data(), rel.size());
+    A.pts_w = S.up(pts_w + (size_t)first[0] * 3, np * 3);
+    A.pts_uv = S.up(pts_uv + (size_t)first[0] * 2, np * 2);
+    A.Ps_prev = S.up(Ps_prev, nf * 3);
+    A.Rs_prev = S.up(Rs_prev, nf * 9);
+    A.Ps_out = S.out<double>(nf * 3);
+    A.Rs_out = S.out<double>(nf * 9);
+    A.n_inliers = S.out<int32_t>(nf);
+    A.inlier = S.out<uint8_t>(np);
+    A.best = S.out<int32_t>(nf);
+    A.n_iters = S.out<int32_t>(nf);
+    A.info = S.out<int32_t>(nf);
+    if (samples) A.samples = S.out<int32_t>(nf * H * 5);
+    if (hyp) A.hyp = S.out<double>(nf * H * 12);
+    if (count) A.count = S.out<int32_t>(nf * H);
+    if (S.failed()) return S.rc();
+    const int rc = swf_internal_pnp_launch(A, st);
+    if (rc) return rc;
+    S.down(h_po.data(), A.Ps_out, h_po.size());
+    S.down(h_ro.data(), A.Rs_out, h_ro.size());
+    S.down(h_ni.data(), A.n_inliers, h_ni.size());
+    S.down(h_in.data(), A.inlier, h_in.size());
+    S.down(h_b.data(), A.best, h_b.size());
+    S.down(h_it.data(), A.n_iters, h_it.size());
+    S.down(h_info.data(), A.info, h_info.size());
+    S.down(h_s.data(), A.samples, h_s.size());
+    S.down(h_h.data(), A.hyp, h_h.size());
+    S.down(h_c.data(), A.count, h_c.size());
+    S.sync();
+    if (S.failed()) return S.rc();
     for (int i = 0; i < n_frames; i++) {
         const int32_t c = h_info[(size_t)i];
         if (code[(size_t)i] != SWF_PNP_OK) {

@@ -31,6 +31,7 @@
 #include <vector>
 #include "../../include/swf_solver.h"
 #include "swf_dev.h"
+#include "swf_stage.h"
 
 void swf_internal_set_error(const std::string& m);
 static int pi_fail(int code, const std::string& m) { swf_internal_set_error(m); return code; }
@@ -466,42 +467,22 @@ extern "C" int swf_preintegrate_batch(const double* samples, const int32_t* firs
     for (int i = 0; i < n_intervals; i++)
         if (first[i + 1] < first[i]) return pi_fail(SWF_E_INVALID, "swf_preintegrate_batch: sample offsets must be non-decreasing");
     size_t ns = (size_t)(first[n_intervals] - first[0]);
-    double *d_s = nullptr, *d_b = nullptr, *d_o = nullptr; int* d_f = nullptr;
     std::vector<int32_t> rel(first, first + n_intervals + 1);
     for (auto& v : rel) v -= first[0];
-    auto cleanup = [&]() { (void)hipFree(d_s); (void)hipFree(d_b); (void)hipFree(d_o); (void)hipFree(d_f); };
-#define PI_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return pi_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    PI_TRY(hipMalloc(&d_s, std::max<size_t>(1, ns) * 7 * sizeof(double)));
-    PI_TRY(hipMalloc(&d_b, (size_t)n_intervals * 6 * sizeof(double)));
-    PI_TRY(hipMalloc(&d_o, (size_t)n_intervals * SWF_PRE_DOUBLES * sizeof(double)));
-    PI_TRY(hipMalloc(&d_f, (size_t)(n_intervals + 1) * sizeof(int)));
-    PI_TRY(hipMemcpyAsync(d_s, samples + (size_t)first[0] * 7, ns * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-    PI_TRY(hipMemcpyAsync(d_b, bias, (size_t)n_intervals * 6 * sizeof(double), hipMemcpyHostToDevice, st));
-    PI_TRY(hipMemcpyAsync(d_f, rel.data(), rel.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    A.samples = d_s; A.first = d_f; A.bias = d_b; A.pre = d_o;
+    HostStage S("swf_preintegrate_batch", st);
+    A.samples = S.up(samples + (size_t)first[0] * 7, ns * 7, 7);
+    A.bias = S.up(bias, (size_t)n_intervals * 6);
+    A.pre = S.out<double>((size_t)n_intervals * SWF_PRE_DOUBLES);
+    A.first = S.up(rel.data(), rel.size());
+    if (S.failed()) return S.rc();
     hipLaunchKernelGGL(k_preintegrate<PI_CONTIG>, dim3((n_intervals + PI_GROUPS - 1) / PI_GROUPS), dim3(64), 0, st, A);
-    PI_TRY(hipGetLastError());
-    PI_TRY(hipMemcpyAsync(pre, d_o, (size_t)n_intervals * SWF_PRE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, st));
-    PI_TRY(hipStreamSynchronize(st));
-#undef PI_TRY
-    cleanup();
-    return SWF_OK;
+    S.check(hipGetLastError(), "hipGetLastError()");
+    S.down(pre, A.pre, (size_t)n_intervals * SWF_PRE_DOUBLES);
+    S.sync();
+    return S.rc();
 }
 
 namespace {
-// device buffers of one host-memory call, freed on every way out
-struct PiBufs {
-    std::vector<void*> p;
-    ~PiBufs() { for (void* q : p) (void)hipFree(q); }
-    hipError_t up(void** d, const void* h, size_t bytes, hipStream_t st) {
-        hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 8));
-        if (e != hipSuccess) return e;
-        p.push_back(*d);
-        return (h && bytes) ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    }
-};
-#define PI_TRYB(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return pi_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 // what the kernel's first pass finds, on host memory: the SWF_IMUF_* code of one frame and its number of cut rows
 int imuf_classify(const double* raw, int n_raw, double t0, double t1, int* rows) {
     *rows = 0;
@@ -544,19 +525,18 @@ extern "C" int swf_preintegrate_runs_batch(const double* samples, int32_t n_samp
             return pi_fail(SWF_E_INVALID, "swf_preintegrate_runs_batch: a run leaves the sample array");
     std::vector<int32_t> rel(run_first, run_first + n_intervals + 1);
     for (auto& v : rel) v -= r0;
-    PiBufs B;
-    void *d_s, *d_r, *d_f, *d_b, *d_o;
-    PI_TRYB(B.up(&d_s, samples, (size_t)n_samples * 7 * sizeof(double), st));
-    PI_TRYB(B.up(&d_r, runs + (size_t)2 * r0, (size_t)nr * 2 * sizeof(int32_t), st));
-    PI_TRYB(B.up(&d_f, rel.data(), rel.size() * sizeof(int32_t), st));
-    PI_TRYB(B.up(&d_b, bias, (size_t)n_intervals * 6 * sizeof(double), st));
-    PI_TRYB(B.up(&d_o, nullptr, (size_t)n_intervals * SWF_PRE_DOUBLES * sizeof(double), st));
-    A.samples = (const double*)d_s; A.runs = (const int*)d_r; A.run_first = (const int*)d_f; A.bias = (const double*)d_b; A.pre = (double*)d_o;
+    HostStage S("swf_preintegrate_runs_batch", st);
+    A.samples = S.up(samples, (size_t)n_samples * 7);
+    A.runs = S.up(runs + (size_t)2 * r0, (size_t)nr * 2);
+    A.run_first = S.up(rel.data(), rel.size());
+    A.bias = S.up(bias, (size_t)n_intervals * 6);
+    A.pre = S.out<double>((size_t)n_intervals * SWF_PRE_DOUBLES);
+    if (S.failed()) return S.rc();
     hipLaunchKernelGGL(k_preintegrate<PI_RUNS>, grid, dim3(64), 0, st, A);
-    PI_TRYB(hipGetLastError());
-    PI_TRYB(hipMemcpyAsync(pre, d_o, (size_t)n_intervals * SWF_PRE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, st));
-    PI_TRYB(hipStreamSynchronize(st));
-    return SWF_OK;
+    S.check(hipGetLastError(), "hipGetLastError()");
+    S.down(pre, A.pre, (size_t)n_intervals * SWF_PRE_DOUBLES);
+    S.sync();
+    return S.rc();
 }
 
 extern "C" int swf_imu_frame_batch(const double* raw, const int32_t* first, int32_t n_frames, const double* t01, const double* seed,
@@ -592,32 +572,30 @@ extern "C" int swf_imu_frame_batch(const double* raw, const int32_t* first, int3
     const size_t ns = (size_t)(first[n_frames] - first[0]), nf = (size_t)n_frames;
     std::vector<int32_t> rel(first, first + n_frames + 1);
     for (auto& v : rel) v -= first[0];
-    PiBufs B;
-    void *d_s, *d_f, *d_t, *d_sd, *d_x, *d_g, *d_fl, *d_c, *d_o, *d_p, *d_i;
-    PI_TRYB(B.up(&d_s, raw + (size_t)first[0] * 7, ns * 7 * sizeof(double), st));
-    PI_TRYB(B.up(&d_f, rel.data(), rel.size() * sizeof(int32_t), st));
-    PI_TRYB(B.up(&d_t, t01, nf * 2 * sizeof(double), st));
-    PI_TRYB(B.up(&d_sd, seed, nf * 6 * sizeof(double), st));
-    PI_TRYB(B.up(&d_x, state, nf * 21 * sizeof(double), st));
-    PI_TRYB(B.up(&d_g, gyrj_prev, nf * 3 * sizeof(double), st));
-    PI_TRYB(B.up(&d_fl, flags, nf * sizeof(int32_t), st));
-    PI_TRYB(B.up(&d_c, nullptr, (ns + nf) * 7 * sizeof(double), st));
-    PI_TRYB(B.up(&d_o, nullptr, nf * SWF_PRE_DOUBLES * sizeof(double), st));
-    PI_TRYB(B.up(&d_p, nullptr, nf * 15 * sizeof(double), st));
-    PI_TRYB(B.up(&d_i, nullptr, nf * sizeof(int32_t), st));
-    A.samples = (const double*)d_s; A.first = (const int*)d_f; A.t01 = (const double*)d_t; A.seed = (const double*)d_sd;
-    A.state = (const double*)d_x; A.gyrj_prev = (const double*)d_g; A.flags = (const int*)d_fl;
-    A.cut = (double*)d_c; A.pre = (double*)d_o; A.pred = (double*)d_p; A.info = (int*)d_i;
-    hipLaunchKernelGGL(k_preintegrate<PI_RAW>, grid, dim3(64), 0, st, A);
-    PI_TRYB(hipGetLastError());
     // a failed frame leaves the caller's cut / pre / pred as they are: the results pass through staging arrays
     std::vector<double> h_c((ns + nf) * 7), h_o(nf * SWF_PRE_DOUBLES), h_p(nf * 15);
     std::vector<int32_t> h_i(nf);
-    PI_TRYB(hipMemcpyAsync(h_c.data(), d_c, h_c.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PI_TRYB(hipMemcpyAsync(h_o.data(), d_o, h_o.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PI_TRYB(hipMemcpyAsync(h_p.data(), d_p, h_p.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PI_TRYB(hipMemcpyAsync(h_i.data(), d_i, h_i.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PI_TRYB(hipStreamSynchronize(st));
+    HostStage S("swf_imu_frame_batch", st);
+    A.samples = S.up(raw + (size_t)first[0] * 7, ns * 7);
+    A.first = S.up(rel.data(), rel.size());
+    A.t01 = S.up(t01, nf * 2);
+    A.seed = S.up(seed, nf * 6);
+    A.state = S.up(state, nf * 21);
+    A.gyrj_prev = S.up(gyrj_prev, nf * 3);
+    A.flags = S.up(flags, nf);
+    A.cut = S.out<double>((ns + nf) * 7);
+    A.pre = S.out<double>(nf * SWF_PRE_DOUBLES);
+    A.pred = S.out<double>(nf * 15);
+    A.info = S.out<int32_t>(nf);
+    if (S.failed()) return S.rc();
+    hipLaunchKernelGGL(k_preintegrate<PI_RAW>, grid, dim3(64), 0, st, A);
+    S.check(hipGetLastError(), "hipGetLastError()");
+    S.down(h_c.data(), A.cut, h_c.size());
+    S.down(h_o.data(), A.pre, h_o.size());
+    S.down(h_p.data(), A.pred, h_p.size());
+    S.down(h_i.data(), A.info, h_i.size());
+    S.sync();
+    if (S.failed()) return S.rc();
     for (int i = 0; i < n_frames; i++) {
         if (h_i[i] != info[i]) return pi_fail(SWF_E_STATE, "swf_imu_frame_batch: the device classified a frame differently from the host");
         if (info[i] != SWF_IMUF_OK) continue;
@@ -627,7 +605,6 @@ extern "C" int swf_imu_frame_batch(const double* raw, const int32_t* first, int3
     }
     return SWF_OK;
 }
-#undef PI_TRYB
 
 // =====================================================================================================================
 // (2) two-view landmark triangulation: FeatureManager::triangulate, the branch every feature with >= 2 observations takes
@@ -733,29 +710,26 @@ extern "C" int swf_triangulate_batch(const double* Ps, const double* Rs, int32_t
         PI_HIPCHK(hipGetLastError());
         return SWF_OK;
     }
-    double* d = nullptr; int* d_s = nullptr;
     const size_t nf = (size_t)std::max(1, n_frames);
-    const size_t doubles = nf * 12 + (size_t)n * 8;        // Ps | Rs | pt0 | pt1 | depth | world
-    auto cleanup = [&]() { (void)hipFree(d); (void)hipFree(d_s); };
-#define TR_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return pi_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    TR_TRY(hipMalloc(&d, doubles * sizeof(double)));
-    TR_TRY(hipMalloc(&d_s, (size_t)n * sizeof(int)));
+    HostStage S("swf_triangulate_batch", st);
+    double* d = S.out<double>(nf * 12 + (size_t)n * 8);        // Ps | Rs | pt0 | pt1 | depth | world
+    int* d_s = S.out<int>((size_t)n);
+    if (S.failed()) return S.rc();      // the sub-buffers below are offsets into d: not formed from a null d
     double* dPs = d; double* dRs = dPs + nf * 3; double* dp0 = dRs + nf * 9; double* dp1 = dp0 + (size_t)n * 2;
     double* ddep = dp1 + (size_t)n * 2; double* dw = ddep + n;
-    TR_TRY(hipMemcpyAsync(dPs, Ps, (size_t)n_frames * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    TR_TRY(hipMemcpyAsync(dRs, Rs, (size_t)n_frames * 9 * sizeof(double), hipMemcpyHostToDevice, st));
-    TR_TRY(hipMemcpyAsync(dp0, pt0, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
-    TR_TRY(hipMemcpyAsync(dp1, pt1, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
-    TR_TRY(hipMemcpyAsync(d_s, start_frame, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    S.put(dPs, Ps, (size_t)n_frames * 3);
+    S.put(dRs, Rs, (size_t)n_frames * 9);
+    S.put(dp0, pt0, (size_t)n * 2);
+    S.put(dp1, pt1, (size_t)n * 2);
+    S.put(d_s, start_frame, (size_t)n);
     A.Ps = dPs; A.Rs = dRs; A.start = d_s; A.pt0 = dp0; A.pt1 = dp1; A.depth = ddep; A.world = dw;
+    if (S.failed()) return S.rc();
     hipLaunchKernelGGL(k_triangulate, dim3((n + 255) / 256), dim3(256), 0, st, A);
-    TR_TRY(hipGetLastError());
-    TR_TRY(hipMemcpyAsync(depth, ddep, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    TR_TRY(hipMemcpyAsync(pts_world, dw, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    TR_TRY(hipStreamSynchronize(st));
-#undef TR_TRY
-    cleanup();
-    return SWF_OK;
+    S.check(hipGetLastError(), "hipGetLastError()");
+    S.down(depth, ddep, (size_t)n);
+    S.down(pts_world, dw, (size_t)n * 3);
+    S.sync();
+    return S.rc();
 }
 
 // =====================================================================================================================
@@ -817,22 +791,15 @@ extern "C" int swf_eval_inverse_depth_batch(const int32_t* kind, const int32_t* 
         if ((k != 2 && (!okp(ix[0]) || !okp(ix[1]))) || !okp(ix[2]) || (k != 0 && !okp(ix[3])) || ix[4] < 0 || ix[4] >= n_lambda)
             return pi_fail(SWF_E_INVALID, "swf_eval_inverse_depth_batch: index out of range");
     }
-    void* bufs[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    auto cleanup = [&]() { for (void* b_ : bufs) (void)hipFree(b_); };
-    const size_t sz[7] = { (size_t)n * sizeof(int), (size_t)n * 5 * sizeof(int), (size_t)n_pose * 7 * sizeof(double), (size_t)n_lambda * sizeof(double),
-                           (size_t)n * 6 * sizeof(double), (size_t)n * 2 * sizeof(double), (size_t)n * 50 * sizeof(double) };
-    const void* src[5] = { kind, idx, poses, lambda, pts };
-#define ID_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return pi_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    for (int b_ = 0; b_ < 7; b_++) ID_TRY(hipMalloc(&bufs[b_], sz[b_]));
-    for (int b_ = 0; b_ < 5; b_++) ID_TRY(hipMemcpyAsync(bufs[b_], src[b_], sz[b_], hipMemcpyHostToDevice, st));
-    A.kind = (const int*)bufs[0]; A.idx = (const int*)bufs[1]; A.poses = (const double*)bufs[2]; A.lambda = (const double*)bufs[3];
-    A.pts = (const double*)bufs[4]; A.r = (double*)bufs[5]; A.J = (double*)bufs[6];
+    HostStage S("swf_eval_inverse_depth_batch", st);
+    A.kind = S.up(kind, (size_t)n); A.idx = S.up(idx, (size_t)n * 5); A.poses = S.up(poses, (size_t)n_pose * 7);
+    A.lambda = S.up(lambda, (size_t)n_lambda); A.pts = S.up(pts, (size_t)n * 6);
+    A.r = S.out<double>((size_t)n * 2); A.J = S.out<double>((size_t)n * 50);
+    if (S.failed()) return S.rc();
     hipLaunchKernelGGL(k_eval_idepth, dim3((n + 127) / 128), dim3(128), 0, st, A);
-    ID_TRY(hipGetLastError());
-    ID_TRY(hipMemcpyAsync(r, bufs[5], sz[5], hipMemcpyDeviceToHost, st));
-    ID_TRY(hipMemcpyAsync(J, bufs[6], sz[6], hipMemcpyDeviceToHost, st));
-    ID_TRY(hipStreamSynchronize(st));
-#undef ID_TRY
-    cleanup();
-    return SWF_OK;
+    S.check(hipGetLastError(), "hipGetLastError()");
+    S.down(r, A.r, (size_t)n * 2);
+    S.down(J, A.J, (size_t)n * 50);
+    S.sync();
+    return S.rc();
 }

@@ -6,20 +6,13 @@
 #include <string>
 #include <vector>
 #include "swf_trackreject.h"
+#include "swf_devutil.h"
+#include "swf_stage.h"
 
 void swf_internal_set_error(const std::string& m);
 static int trk_fail(int code, const std::string& m) { swf_internal_set_error(m); return code; }
 
 namespace {
-
-__device__ __forceinline__ unsigned long long trk_mix(unsigned long long x) {     // splitmix64's output at state x + 0x9E37..
-    unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ bool trk_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 // PinholeFullCamera::liftProjective (:535-607): nine fixed-point steps in the reference's operation order.  Contraction is off, so
 // every operation rounds once and a float64 evaluation of the same expressions gives the same bits.
@@ -65,20 +58,6 @@ __device__ __forceinline__ bool trk_inlier(const double F[9], double u1, double 
     return d1 <= thr2 && d2 <= thr2;
 }
 
-// OpenCV's RANSACUpdateNumIters with ep = (n - count) / n; the power is m - 1 products
-__device__ __forceinline__ int trk_update_iters(double conf, int count, int n, int m, int n_iters) {
-    const double p = fmin(fmax(conf, 0.0), 1.0);
-    const double ep = fmin(fmax((double)(n - count) / (double)n, 0.0), 1.0);
-    const double num = fmax(1.0 - p, DBL_MIN), w = 1.0 - ep;
-    double wm = w;
-    for (int i = 1; i < m; i++) wm *= w;
-    const double d = 1.0 - wm;
-    if (d < DBL_MIN) return 0;
-    const double ln = log(num), ld = log(d);
-    if (ld >= 0.0 || -ln >= (double)n_iters * -ld) return n_iters;
-    return (int)rint(ln / ld);
-}
-
 #define TRK_OFF(i) ((i) * 9 - (i) * ((i) - 1) / 2)      // reflector i holds components i .. 8
 
 // Hypothesis k of a pair of n points (s_p: u1 | v1 | u2 | v2, each TRK_NMAX long): the sample, and F by the 8-point algorithm.
@@ -92,7 +71,7 @@ __device__ __forceinline__ bool trk_hypothesis(const double* s_p, int n, int k, 
         for (int q = 0; q < 8; q++) smp[q] = q;
         got = 8;
     } else for (int j = 0; j < TRK_DRAWS && got < 8; j++) {
-        const unsigned long long x = trk_mix(seed + 64ull * (unsigned long long)k + (unsigned long long)j);
+        const unsigned long long x = swf_mix(seed + 64ull * (unsigned long long)k + (unsigned long long)j);
         const int idx = (int)(((x >> 32) * (unsigned long long)n) >> 32);
         bool dup = false;
 #pragma unroll
@@ -210,7 +189,7 @@ __device__ __forceinline__ bool trk_hypothesis(const double* s_p, int n, int k, 
         F[6 + j] = tx2 * M[j] + ty2 * M[3 + j] + M[6 + j];
     }
 #pragma unroll
-    for (int i = 0; i < 9; i++) ok = ok && trk_finite(F[i]);
+    for (int i = 0; i < 9; i++) ok = ok && swf_finite(F[i]);
     return ok;
 }
 
@@ -229,14 +208,14 @@ __global__ void __launch_bounds__(TRK_THREADS) k_track_reject(TrkArgs A) {
     const bool as_float = (A.flags & 1) != 0;
     // ---------------------------------------------------------------- stage the pixels; the non-finite test is on what is staged
     const double dt = A.dt[f];
-    bool bad = !trk_finite(dt) || !(dt > 0.0);
+    bool bad = !swf_finite(dt) || !(dt > 0.0);
     for (int i = tid; i < n; i += TRK_THREADS) {
         const size_t g = (size_t)p0 + i;
         double c[4] = { A.cur_px[2 * g], A.cur_px[2 * g + 1], A.prev_px[2 * g], A.prev_px[2 * g + 1] };
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if (as_float) c[k] = (double)(float)c[k];
-            bad |= !trk_finite(c[k]);
+            bad |= !swf_finite(c[k]);
             s_p[k * TRK_NMAX + i] = c[k];
         }
     }
@@ -296,7 +275,7 @@ __global__ void __launch_bounds__(TRK_THREADS) k_track_reject(TrkArgs A) {
                 const int c = s_count[kk];
                 if (c > max(best_count, 7)) {
                     best = kk; best_count = c;
-                    n_iters = trk_update_iters(A.confidence, c, n, 8, n_iters);
+                    n_iters = swf_update_iters(A.confidence, c, n, 8, n_iters);
                 }
             }
             s_scan[0] = best; s_scan[1] = n_iters; s_scan[2] = best_count; s_scan[4] = kk;
@@ -437,64 +416,47 @@ extern "C" int swf_track_reject_batch(int32_t n_pairs, const int32_t* first, con
     const size_t nf = (size_t)n_pairs, np = (size_t)(first[n_pairs] - first[0]), H = (size_t)iterations;
     std::vector<int32_t> rel(first, first + n_pairs + 1);
     for (auto& v : rel) v -= first[0];
-    std::vector<void*> bufs;
-    auto cleanup = [&]() { for (void* p : bufs) (void)hipFree(p); };
-#define TRK_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return trk_fail(SWF_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    auto dev = [&](size_t bytes, const void* src, void** out) -> hipError_t {
-        hipError_t rc = hipMalloc(out, std::max<size_t>(bytes, 8));
-        if (rc != hipSuccess) return rc;
-        bufs.push_back(*out);
-        return src && bytes ? hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
-    void *d_f, *d_c, *d_p, *d_dt, *d_info, *d_st = nullptr, *d_k = nullptr, *d_ni = nullptr, *d_b = nullptr, *d_it = nullptr, *d_F = nullptr;
-    void *d_uc = nullptr, *d_up = nullptr, *d_v = nullptr, *d_s = nullptr, *d_h = nullptr, *d_n = nullptr;
-    TRK_TRY(dev(rel.size() * sizeof(int32_t), rel.data(), &d_f));
-    TRK_TRY(dev(np * 2 * sizeof(double), cur_px + (size_t)first[0] * 2, &d_c));
-    TRK_TRY(dev(np * 2 * sizeof(double), prev_px + (size_t)first[0] * 2, &d_p));
-    TRK_TRY(dev(nf * sizeof(double), dt, &d_dt));
-    TRK_TRY(dev(nf * sizeof(int32_t), nullptr, &d_info));
-    if (status) TRK_TRY(dev(np, nullptr, &d_st));
-    if (keep_idx) TRK_TRY(dev(np * sizeof(int32_t), nullptr, &d_k));
-    if (n_inliers) TRK_TRY(dev(nf * sizeof(int32_t), nullptr, &d_ni));
-    if (best) TRK_TRY(dev(nf * sizeof(int32_t), nullptr, &d_b));
-    if (n_iters) TRK_TRY(dev(nf * sizeof(int32_t), nullptr, &d_it));
-    if (F) TRK_TRY(dev(nf * 9 * sizeof(double), nullptr, &d_F));
-    if (un_cur) TRK_TRY(dev(np * 2 * sizeof(double), nullptr, &d_uc));
-    if (un_prev) TRK_TRY(dev(np * 2 * sizeof(double), nullptr, &d_up));
-    if (velocity) TRK_TRY(dev(np * 2 * sizeof(double), nullptr, &d_v));
-    if (samples) TRK_TRY(dev(nf * H * 8 * sizeof(int32_t), nullptr, &d_s));
-    if (hyp) TRK_TRY(dev(nf * H * 9 * sizeof(double), nullptr, &d_h));
-    if (count) TRK_TRY(dev(nf * H * sizeof(int32_t), nullptr, &d_n));
-    A.first = (const int*)d_f; A.cur_px = (const double*)d_c; A.prev_px = (const double*)d_p; A.dt = (const double*)d_dt;
-    A.status = (unsigned char*)d_st; A.keep_idx = (int*)d_k; A.n_inliers = (int*)d_ni; A.best = (int*)d_b; A.n_iters = (int*)d_it;
-    A.info = (int*)d_info; A.F = (double*)d_F; A.un_cur = (double*)d_uc; A.un_prev = (double*)d_up; A.velocity = (double*)d_v;
-    A.samples = (int*)d_s; A.hyp = (double*)d_h; A.count = (int*)d_n;
-    const int rc = swf_internal_trk_launch(A, st);
-    if (rc) { cleanup(); return rc; }
     // a pair leaves what it does not write as the caller had it: the results pass through staging arrays
     std::vector<double> h_F(F ? nf * 9 : 0), h_uc(un_cur ? np * 2 : 0), h_up(un_prev ? np * 2 : 0), h_v(velocity ? np * 2 : 0), h_h(hyp ? nf * H * 9 : 0);
     std::vector<int32_t> h_info(nf), h_k(keep_idx ? np : 0), h_ni(n_inliers ? nf : 0), h_b(best ? nf : 0), h_it(n_iters ? nf : 0);
     std::vector<int32_t> h_s(samples ? nf * H * 8 : 0), h_n(count ? nf * H : 0);
     std::vector<uint8_t> h_st(status ? np : 0);
-    auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-    };
-    TRK_TRY(down(h_info.data(), d_info, nf * sizeof(int32_t)));
-    TRK_TRY(down(h_st.data(), d_st, h_st.size()));
-    TRK_TRY(down(h_k.data(), d_k, h_k.size() * sizeof(int32_t)));
-    TRK_TRY(down(h_ni.data(), d_ni, h_ni.size() * sizeof(int32_t)));
-    TRK_TRY(down(h_b.data(), d_b, h_b.size() * sizeof(int32_t)));
-    TRK_TRY(down(h_it.data(), d_it, h_it.size() * sizeof(int32_t)));
-    TRK_TRY(down(h_F.data(), d_F, h_F.size() * sizeof(double)));
-    TRK_TRY(down(h_uc.data(), d_uc, h_uc.size() * sizeof(double)));
-    TRK_TRY(down(h_up.data(), d_up, h_up.size() * sizeof(double)));
-    TRK_TRY(down(h_v.data(), d_v, h_v.size() * sizeof(double)));
-    TRK_TRY(down(h_s.data(), d_s, h_s.size() * sizeof(int32_t)));
-    TRK_TRY(down(h_h.data(), d_h, h_h.size() * sizeof(double)));
-    TRK_TRY(down(h_n.data(), d_n, h_n.size() * sizeof(int32_t)));
-    TRK_TRY(hipStreamSynchronize(st));
-#undef TRK_TRY
-    cleanup();
+    HostStage S("swf_track_reject_batch", st);
+    A.first = S.up(rel.data(), rel.size());
+    A.cur_px = S.up(cur_px + (size_t)first[0] * 2, np * 2);
+    A.prev_px = S.up(prev_px + (size_t)first[0] * 2, np * 2);
+    A.dt = S.up(dt, nf);
+    A.info = S.out<int32_t>(nf);
+    if (status) A.status = S.out<uint8_t>(np);
+    if (keep_idx) A.keep_idx = S.out<int32_t>(np);
+    if (n_inliers) A.n_inliers = S.out<int32_t>(nf);
+    if (best) A.best = S.out<int32_t>(nf);
+    if (n_iters) A.n_iters = S.out<int32_t>(nf);
+    if (F) A.F = S.out<double>(nf * 9);
+    if (un_cur) A.un_cur = S.out<double>(np * 2);
+    if (un_prev) A.un_prev = S.out<double>(np * 2);
+    if (velocity) A.velocity = S.out<double>(np * 2);
+    if (samples) A.samples = S.out<int32_t>(nf * H * 8);
+    if (hyp) A.hyp = S.out<double>(nf * H * 9);
+    if (count) A.count = S.out<int32_t>(nf * H);
+    if (S.failed()) return S.rc();
+    const int rc = swf_internal_trk_launch(A, st);
+    if (rc) return rc;
+    S.down(h_info.data(), A.info, h_info.size());
+    S.down(h_st.data(), A.status, h_st.size());
+    S.down(h_k.data(), A.keep_idx, h_k.size());
+    S.down(h_ni.data(), A.n_inliers, h_ni.size());
+    S.down(h_b.data(), A.best, h_b.size());
+    S.down(h_it.data(), A.n_iters, h_it.size());
+    S.down(h_F.data(), A.F, h_F.size());
+    S.down(h_uc.data(), A.un_cur, h_uc.size());
+    S.down(h_up.data(), A.un_prev, h_up.size());
+    S.down(h_v.data(), A.velocity, h_v.size());
+    S.down(h_s.data(), A.samples, h_s.size());
+    S.down(h_h.data(), A.hyp, h_h.size());
+    S.down(h_n.data(), A.count, h_n.size());
+    S.sync();
+    if (S.failed()) return S.rc();
     for (int i = 0; i < n_pairs; i++) {
         const int32_t c = h_info[(size_t)i];
         if (code[(size_t)i] == SWF_TRK_BAD_INPUT) {
