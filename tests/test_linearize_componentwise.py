@@ -1,0 +1,472 @@
+"""The factor linearisation — the residual rows and Jacobian blocks that d_eval_imu / imu_unwhitened / imu_whiten_store, proj_core /
+d_eval_proj_fs, d_eval_scalar, k_eval_idp and d_eval_prior write, and the costs of their cost-only twins — held to a longdouble referee
+ENTRY BY ENTRY.  Referee and brackets: tests/np_linearize.py; windows: tests/linearize_cases.py.
+
+This is the link between the producer kernels (test_producers.py) and the reduced system (test_schur_componentwise.py, whose referee takes
+the implementation's own (r, J) as given).  Rule: every entry of r and J satisfies |q - referee| <= M x 2^-52 x bracket(q), no mask; where
+the bracket is exactly zero the value is the referee's exactly (structural zeros, the prior's copied J, +-1).  The window cost
+1/2 sum rho(|r|^2) is held to its own bracket.  Composite IMU-GNSS rows stay with np_dense.composite_dense (skipped by position).
+
+The constants are measured on the CPU, never on the device: per factor family, M = ceil(8 x the largest ratio either of two float64 routes
+shows over every case) — route 1 the oracle (export_jacobian, evaluate), route 2 the referee itself at np.float64 with every sum of
+products taken from the other end (order="alt").  test_constants_are_the_measured_ones prints every ratio and asserts them.  Sharpness: the
+largest ratios are IMU 0.40 / 0.99 (r / J), GNSS 0.24 / 0.41, inverse depth 0.23 / 0.19, prior 0.19 (its J is a copy: bit for bit),
+projection 0.061 / 0.087, cost 0.12 — all inside the project's window [1/32, 4]; the running bound is loosest on the projection
+factors, whose bracket counts every product of the two rotation chains.
+
+Largest device ratios on MI355X (r / J; every GPU test prints its own): IMU 0.419 / 0.799, projection 0.049 / 0.090,
+inverse depth 0.140 / 0.190, GNSS 0.254 / 0.412, prior 0.186 / exact, cost 0.081; batch windows and launch knobs give the single window's
+bits.
+
+The older rules stay where they are (np_dense.check_linearization, test_iterates_and_prior_reset.py); old_rules() below restates their two
+tightest forms — max|J - J_ref| <= 1e-10 max|J_ref| over the window, |r - r_ref| <= 1e-9 max(1, |r|_inf) per factor (GNSS ranges: 1e-7 x
+weight) — so that the sensitivity tests can print both readings.  What they show: every control fails the new rule, by 6.3e3 to
+4.8e6 brackets; every control passes the old Jacobian rule (readings of 1e-7 to 0.08 of its limit); the old residual rule passes the
+dq_dbg control (1.2e-3 of its limit) and both structural errors (they leave r alone), and does see the other four scaled inputs: the
+lever arm 6.4, the landmark coordinate 4.3 (the landmark at 0.3 m), the prior x0 125 and the satellite coordinate 4.0e4 times its limit
+(a 2.6e7 m number scaled by 1 + 1e-9 moves the range by centimetres).  So for those four it is the Jacobian alone that went unjudged."""
+import functools
+import math
+
+import numpy as np
+import pytest
+
+import linearize_cases as lc
+import np_linearize as nl
+from rtk_visual_inertial_navigation_amd.flat import default_options
+
+EPS = nl.EPS
+# M = ceil(8 x the largest CPU ratio); the ratio, the route and the case it came from (test_constants_are_the_measured_ones prints them)
+M_R = dict(imu=4.0,     # 0.404  both routes, proj_depths
+           proj=1.0,    # 0.061  numpy alt, prior_17 / prior_130
+           idp=2.0,     # 0.231  numpy alt, idp_stereo
+           gnss=2.0,    # 0.241  both routes, idp_stereo / prior_16
+           prior=2.0)   # 0.186  both routes, imu_bias_far
+M_J = dict(imu=8.0,     # 0.990  numpy alt, gnss_spp_fixed
+           proj=1.0,    # 0.087  oracle, proj_trivial
+           idp=2.0,     # 0.190  both routes, idp_stereo
+           gnss=4.0,    # 0.412  both routes, gnss_rover_only
+           prior=0.0)   # 0      the exported J is the input J, bit for bit
+M_COST = 1.0            # 0.118  oracle, imu_bias_far
+VACUOUS = 1e-3
+FLOOR = 2.0 ** -26      # entries below this share of their row's largest entry are counted, and judged all the same
+FLOOR_CAP = 0.25
+OLD_J, OLD_R, OLD_R_GNSS = 1e-10, 1e-9, 1e-7
+
+needs_longdouble = pytest.mark.skipif(np.finfo(np.longdouble).eps >= np.finfo(np.float64).eps,
+                                      reason="np.longdouble is no wider than float64 on this platform")
+gpu = pytest.mark.gpu
+
+
+# ---------------------------------------------------------------------------------------------------------------- the rule
+def group_mask(ref, g):
+    return np.array([nl.GROUP.get(nl.FAMILIES[f]) == g for f in ref["fam"]], bool)
+
+
+def row_constants(ref, table):
+    return np.array([table.get(nl.GROUP.get(nl.FAMILIES[f]), np.nan) for f in ref["fam"]])
+
+
+def rule(r, J, ref):
+    """(passes, {group: (largest ratio of r, largest ratio of J)}): every entry of every non-composite row against its own constant;
+    a zero bracket (or a zero constant) admits only the referee's own value"""
+    qr, qJ = nl.ratio(r, ref["r"], ref["b_r"]), nl.ratio(J, ref["J"], ref["b_J"])
+    keep = ~np.isnan(row_constants(ref, M_R))
+    ok = bool(np.all(qr[keep] <= row_constants(ref, M_R)[keep]) and np.all(qJ[keep] <= row_constants(ref, M_J)[keep][:, None]))
+    return ok, {g: (float(qr[group_mask(ref, g)].max()), float(qJ[group_mask(ref, g)].max())) for g in nl.GROUPS if group_mask(ref, g).any()}
+
+
+def cost_ratio(cost, ref):
+    return float(abs(np.longdouble(cost) - ref["cost"]) / (EPS * ref["b_cost"]))
+
+
+def show(label, w, cost=None):
+    print("%-40s deviation / bracket (r, J): %s%s" % (label, "  ".join("%s %.3f %.3f" % (g, a, b) for g, (a, b) in w.items()),
+                                                     "" if cost is None else "  cost %.3f" % cost))
+
+
+def old_rules(r, J, ref):
+    """(reading of the whole-window Jacobian rule / 1e-10, largest reading of the per-factor residual rule / its own limit)"""
+    Jr, rr = ref["J"].astype(np.float64), ref["r"].astype(np.float64)
+    keep = ~np.isnan(rr)
+    j = float(np.abs(J[keep] - Jr[keep]).max() / np.abs(Jr[keep]).max()) / OLD_J
+    worst = 0.0
+    for f in np.unique(ref["fac"][keep]):
+        m = ref["fac"] == f
+        name = nl.FAMILIES[ref["fam"][m][0]]
+        if name in ("cp", "pr", "spr", "scp"):
+            lim = OLD_R_GNSS * float(np.abs(Jr[m]).max()) + 1e-9          # the largest entry of the row is the clock column's: the weight
+        else:
+            lim = OLD_R * max(1.0, float(np.abs(rr[m]).max()))
+        worst = max(worst, float(np.abs(r[m] - rr[m]).max()) / lim)
+    return j, worst
+
+
+def check(label, r, J, cost, ref):
+    """the whole rule on one implementation's export, with the 2 M control on the weakest entry of every family; returns the ratios"""
+    ok, w = rule(r, J, ref)
+    c = None if cost is None or ref["cost"] is None else cost_ratio(cost, ref)
+    show(label, w, c)
+    assert ok, (label, w)
+    assert c is None or c <= M_COST, (label, "cost", c)
+    for g in w:
+        e = nl.weakest_entry(ref, g)
+        if e is None or M_J[g] == 0:
+            continue
+        Jm = np.array(ref["J"], np.longdouble)
+        Jm[e] += 2 * M_J[g] * EPS * ref["b_J"][e]
+        mut = dict(ref, J=Jm)
+        assert not rule(r, J, mut)[0], (label, g, "blind to 2 M brackets on the weakest entry", e)
+    return w, c
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU routes, cached
+@functools.lru_cache(maxsize=None)
+def cpu_case(name):
+    import oracle_binding as ob
+    w = lc.window(name)
+    ref = nl.linearize(w)
+    alt = nl.linearize(w, np.float64, "alt")
+    r, J = ob.export_jacobian(w)
+    cost, _ = ob.evaluate(w)
+    return dict(w=w, ref=ref, oracle=(r, J, cost), numpy=(alt["r"], alt["J"], float(alt["cost"])))
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU tier
+REACHES = {
+    "imu_1": lambda f: f["n_imu"] == 1, "imu_7": lambda f: f["n_imu"] == 7, "imu_8": lambda f: f["n_imu"] == 8, "imu_9": lambda f: f["n_imu"] == 9,
+    "imu_const": lambda f: 0 in f["const"] and f["n_pose"] + 2 in f["const"],
+    "imu_bias_far": lambda f: 0.05 <= f["bias_gap"] <= 0.2, "imu_turn": lambda f: f["turn"] > np.pi / 2,
+    "imu_off_unit": lambda f: 1e-9 < f["q_off_unit"] < 1e-7, "imu_long": lambda f: 0.99 < f["T"] < 1.01,
+    "proj_trivial": lambda f: f["loss_a"] == 0.0, "proj_256": lambda f: f["n_proj"] == 256, "proj_257": lambda f: f["n_proj"] == 257,
+    "proj_const_lm": lambda f: f["n_pose"] + f["n_sb"] in f["const"],
+    "proj_var_ex": lambda f: f["n_pose"] - 1 not in f["const"], "proj_var_ex_head": lambda f: f["n_pose"] - 1 not in f["const"],
+    "idp_short": lambda f: f["kinds"] == [0] and f["track"] <= 7, "idp_long": lambda f: f["track"] == 16, "idp_stereo": lambda f: f["kinds"] == [0, 1, 2],
+    "gnss_edges": lambda f: f["cp_flags"] == [0.0, 1.0] and 5.0 in f["elevations"] and 85.0 in f["elevations"],
+    "gnss_doppler": lambda f: f["n_dop"] > 0, "gnss_spp_fixed": lambda f: f["n_spr"] > 0 and f["n_scp"] > 0 and f["n_fix"] == 3,
+    "gnss_rover_only": lambda f: f["n_cp"] == 0 and f["n_pr"] == 0 and f["n_spr"] > 0 and f["n_scp"] > 0,
+    "prior_15": lambda f: f["prior_dim"] == [15], "prior_16": lambda f: f["prior_dim"] == [16], "prior_17": lambda f: f["prior_dim"] == [17],
+    "prior_29": lambda f: f["prior_dim"] == [29], "prior_33": lambda f: f["prior_dim"] == [33], "prior_65": lambda f: f["prior_dim"] == [65],
+    "prior_97": lambda f: f["prior_dim"] == [97], "prior_130": lambda f: f["prior_dim"] == [130], "prior_516": lambda f: f["prior_dim"] == [516],
+    "prior_flip": lambda f: f["prior_dim"] == [21],
+}
+PRIOR_CHUNKS = {"prior_65": 1, "prior_97": 4, "prior_130": 5, "prior_516": 17}
+
+
+@needs_longdouble
+@pytest.mark.parametrize("name", list(lc.CASES))
+def test_case_reaches_its_branch(name):
+    """what the window or the plan shows of the branch the case exists for; the plan accepts the window; no elevation near a float32 tie"""
+    from test_plan_host import plan_check
+    w = lc.window(name)
+    f = lc.facts(w)
+    assert name not in REACHES or REACHES[name](f), (name, f)
+    rc, err, info = plan_check([w])
+    assert rc == 0, (name, err)
+    if name in PRIOR_CHUNKS:
+        assert info["n_pch"] == PRIOR_CHUNKS[name], (name, info)
+    assert all(nl.sine_is_safe(e) for e in lc.elevations(w)), name
+    ref = cpu_case(name)["ref"]
+    if name == "proj_depths":
+        assert 0.15 < f["depths"][0] < 0.35 and f["depths"][-1] > 75.0, f["depths"]
+    if name == "proj_outlier":                 # corrected squared norms s / (1 + s) for a = 1: observation 3 above 1e4, observation 5 at 2e-8
+        s = [float((ref["r"][2 * o:2 * o + 2].astype(np.float64) ** 2).sum()) for o in (3, 5)]
+        assert s[0] > 0.9999 and 1e-9 < s[1] < 1e-7, s
+    if name == "prior_flip":                   # the first kept pose: w of q0^-1 q negative, 2 |vec| about 0.15
+        assert f["prior_w"][0] < 0 and 0.1 < 2 * math.sqrt(1 - f["prior_w"][0] ** 2) < 0.35, f["prior_w"]
+
+
+@needs_longdouble
+def test_constants_are_the_measured_ones():
+    """Both float64 routes over every case: every ratio printed, every one within its constant, no constant padded (the largest ratio
+    lies within a factor of two of M / 8), and every family's largest ratio inside the sharpness window [1/32, 4]."""
+    top_r, top_J, top_c = {g: (0.0, "") for g in nl.GROUPS}, {g: (0.0, "") for g in nl.GROUPS}, (0.0, "")
+    for name in lc.CASES:
+        c = cpu_case(name)
+        for route in ("oracle", "numpy"):
+            r, J, cost = c[route]
+            ok, w = rule(r, J, c["ref"])
+            cr = cost_ratio(cost, c["ref"])
+            show("%s, %s:" % (name, route), w, cr)
+            assert ok and cr <= M_COST, (name, route, w, cr)
+            for g, (a, b) in w.items():
+                if a > top_r[g][0]:
+                    top_r[g] = (a, "%s, %s" % (name, route))
+                if b > top_J[g][0]:
+                    top_J[g] = (b, "%s, %s" % (name, route))
+            if cr > top_c[0]:
+                top_c = (cr, "%s, %s" % (name, route))
+    rows = [("M_R[%s]" % g, top_r[g], M_R[g]) for g in nl.GROUPS] + [("M_J[%s]" % g, top_J[g], M_J[g]) for g in nl.GROUPS] + [("M_COST", top_c, M_COST)]
+    for label, (v, where), m in rows:
+        print("%-12s largest ratio %.3f (%s) -> ceil(8 x) = %d, constant %d" % (label, v, where, math.ceil(8 * v), m))
+    for label, (v, where), m in rows:
+        assert m == math.ceil(8 * v), (label, v, where, m)
+        assert v == 0 or 1 / 32 <= v <= 4, (label, v, "outside the sharpness window")
+
+
+@needs_longdouble
+@pytest.mark.parametrize("name", list(lc.CASES))
+def test_oracle_and_numpy_pass_the_componentwise_rule(name):
+    """the CPU tier proper: both float64 routes within the constants on every entry, zero-bracket entries exact, the cost within its
+    bracket, and the rule sensitive to 2 M brackets on the weakest expected Jacobian entry of each family"""
+    c = cpu_case(name)
+    for route in ("oracle", "numpy"):
+        r, J, cost = c[route]
+        check("%s, %s:" % (name, route), r, J, cost, c["ref"])
+    ref = c["ref"]
+    print("%s: %d rows, %d entries of J with a zero bracket (exact), %d judged against one" % (name, ref["r"].size, int((ref["b_J"] == 0).sum()), int((ref["b_J"] > 0).sum())))
+
+
+@needs_longdouble
+def test_composite_rows_are_skipped_by_position():
+    """a window with composite IMU-GNSS factors and landmarks: the referee leaves the composite rows (the last rows of the export) to
+    np_dense.composite_dense and judges every other row of the oracle's export"""
+    import composite_gen as cg
+    import oracle_binding as ob
+    w = cg.make_window(np.random.default_rng(191), 5, 2, 8, F=30)
+    ref = nl.linearize(w)
+    n = ref["n_comp_rows"]
+    assert n == sum(30 + int(N) for N in w.a["comp_N"]) > 0 and ref["cost"] is None
+    assert np.isnan(ref["r"][-n:].astype(np.float64)).all() and not np.isnan(ref["r"][:-n].astype(np.float64)).any()
+    r, J = ob.export_jacobian(w)
+    assert r.size == ref["r"].size
+    with np.errstate(invalid="ignore"):
+        ok, wr = rule(r, J, ref)
+    show("composite + landmarks, oracle, %d composite rows skipped:" % n, wr)
+    assert ok, wr
+
+
+@needs_longdouble
+@pytest.mark.parametrize("name", list(lc.CASES))
+def test_no_vacuous_judgement(name):
+    """On every case, by the referee alone: M 2^-52 bracket <= 1e-3 |entry| for every non-zero Jacobian entry of at least 2^-26 of its
+    row's largest; the entries below that floor are counted (they are judged by the rule all the same) and stay below 25 % of the
+    non-zeros per family; M 2^-52 bracket <= 1e-3 x the row's un-cancelled scale for every residual row."""
+    ref = cpu_case(name)["ref"]
+    Ja = np.abs(ref["J"].astype(np.float64))
+    for g in nl.GROUPS:
+        m = group_mask(ref, g)
+        if not m.any():
+            continue
+        A, B = Ja[m], ref["b_J"][m]
+        nz = A > 0
+        if nz.any():
+            above = nz & (A >= FLOOR * A.max(axis=1, keepdims=True))
+            share = 1.0 - above.sum() / nz.sum()
+            worst = float((M_J[g] * EPS * B[above] / A[above]).max())
+            print("%s, %s: %d non-zero entries, %d (%.2f %%) below 2^-26 of their row's largest; M 2^-52 bracket / |entry| at most %.2e"
+                  % (name, g, nz.sum(), nz.sum() - above.sum(), 100 * share, worst))
+            assert worst <= VACUOUS, (name, g, worst)
+            assert share < FLOOR_CAP, (name, g, share)
+        with np.errstate(divide="ignore", invalid="ignore"):      # (a row whose bracket is zero is exact: the anchor of a scalar at zero)
+            rw = float(np.where(ref["b_r"][m] == 0, 0.0, M_R[g] * EPS * ref["b_r"][m] / ref["scale"][m]).max())
+        print("%s, %s: M 2^-52 bracket / un-cancelled scale of the residual rows at most %.2e" % (name, g, rw))
+        assert rw <= VACUOUS, (name, g, rw)
+
+
+# the controls the old per-factor residual rule does see (readings 6.4, 4.3, 4.0e4 and 125 times its limit); it reads 1.2e-3 on dq_dbg
+OLD_RESIDUAL_RULE_CATCHES = ("pbg", "landmark", "satellite", "x0")
+
+
+def _scaled(name, what):
+    """a copy of the case's window with ONE input scaled by 1 + 1e-9"""
+    w = cpu_case(name)["w"].copy()
+    k = 1.0 + 1e-9
+    if what == "dq_dbg":
+        w.a["imu_pre"].reshape(-1, 293)[0, 34 + int(np.argmax(np.abs(w.a["imu_pre"].reshape(-1, 293)[0, 34:43])))] *= k
+    elif what == "pbg":
+        w.pbg = w.pbg.copy()
+        w.pbg[int(np.argmax(np.abs(w.pbg)))] *= k
+    elif what == "landmark":
+        lm = w.a["lm"].reshape(-1)
+        lm[int(np.argmin(np.where(lm != 0, np.abs(lm), np.inf)))] *= k
+    elif what == "satellite":
+        d = w.a["cp_dat"].reshape(-1, 9)
+        d[0, int(np.argmin(np.abs(d[0, :3])))] *= k
+    elif what == "x0":
+        w.a["prior_x0"][int(np.argmax(np.abs(w.a["prior_x0"][:3])))] *= k
+    return w
+
+
+@needs_longdouble
+@pytest.mark.parametrize("name,what", [("imu_bias_far", "dq_dbg"), ("gnss_doppler", "pbg"), ("proj_depths", "landmark"),
+                                       ("gnss_edges", "satellite"), ("prior_29", "x0")])
+def test_one_input_scaled_fails_the_new_rule(name, what):
+    """one input scaled by 1 + 1e-9, the float64 referee on the changed window against the longdouble referee of the unchanged one: the
+    componentwise rule fails; the readings of the old rules are printed next to it and the old Jacobian rule passes every one"""
+    ref = cpu_case(name)["ref"]
+    mut = nl.linearize(_scaled(name, what), np.float64)
+    ok, w = rule(mut["r"], mut["J"], ref)
+    oj, orr = old_rules(mut["r"], mut["J"], ref)
+    show("%s, %s x (1 + 1e-9):" % (name, what), w)
+    print("   old rules: Jacobian %.3g of its limit (1e-10 max|J|), residual %.3g of its limit" % (oj, orr))
+    assert not ok, (name, what, w)
+    assert oj < 1.0, (name, what, oj)
+    assert (orr >= 1.0) == (what in OLD_RESIDUAL_RULE_CATCHES), (name, what, orr)
+
+
+@needs_longdouble
+def test_structural_errors_in_the_export_fail_the_new_rule():
+    """two errors injected into a copy of the oracle's export, each where it is weakest: the columns of two 3-column blocks of one IMU row
+    swapped, and sr dropped from one projection row (the row of the smallest Cauchy argument).  The componentwise rule fails both; the
+    old rules pass both."""
+    # IMU: the row and pair of blocks whose swap moves the entries MOST while staying under half the old rule's limit
+    c = cpu_case("imu_bias_far")
+    r, J, _ = c["oracle"]
+    ref = c["ref"]
+    cap = 0.5 * OLD_J * float(np.abs(J).max())
+    best = None
+    for i in np.flatnonzero(group_mask(ref, "imu")):
+        cols = np.flatnonzero(ref["b_J"][i] > 0)
+        blocks = sorted(set(int(k) // 3 * 3 for k in cols))
+        for a in blocks:
+            for b in blocks:
+                if a < b:
+                    d = float(np.abs(J[i, a:a + 3] - J[i, b:b + 3]).max())
+                    if 0 < d < cap and (best is None or d > best[0]):
+                        best = (d, i, a, b)
+    d, i, a, b = best
+    Jm = J.copy()
+    Jm[i, a:a + 3], Jm[i, b:b + 3] = J[i, b:b + 3], J[i, a:a + 3]
+    ok, w = rule(r, Jm, ref)
+    oj, orr = old_rules(r, Jm, ref)
+    show("IMU row %d, columns %d.. and %d.. swapped (entries move by %.2e):" % (i, a, b, d), w)
+    print("   old rules: Jacobian %.3g of its limit, residual %.3g of its limit" % (oj, orr))
+    assert not ok and oj < 1.0 and orr < 1.0, (w, oj, orr)
+    # projection: sr dropped from the Jacobian of one row of observation 5 of proj_outlier (1e-4 from its prediction: sr = 1 - 5e-9)
+    c = cpu_case("proj_outlier")
+    r, J, _ = c["oracle"]
+    ref = c["ref"]
+    s = float((r[10:12] ** 2).sum())
+    sr = math.sqrt(1.0 - s)                      # s is the CORRECTED squared norm s0 / (1 + s0): sr^2 = 1 / (1 + s0) = 1 - s
+    Jm = J.copy()
+    Jm[10] /= sr
+    ok, w = rule(r, Jm, ref)
+    oj, orr = old_rules(r, Jm, ref)
+    show("projection row 10 without sr (1 - sr = %.2e):" % (1 - sr), w)
+    print("   old rules: Jacobian %.3g of its limit, residual %.3g of its limit" % (oj, orr))
+    assert sr < 1.0 and not ok and oj < 1.0 and orr < 1.0, (sr, w, oj, orr)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU tier
+def solve_at_uploaded_state(ws):
+    """(BatchSolver, summaries) after an assemble-and-eliminate-only solve: the linearisation sits at the uploaded state"""
+    from rtk_visual_inertial_navigation_amd import solver
+    bs = solver.BatchSolver([w.copy() for w in ws])
+    sms = bs.solve(default_options(step_mode=1), download=False)
+    return bs, sms
+
+
+@gpu
+@needs_longdouble
+@pytest.mark.parametrize("name", list(lc.CASES))
+def test_device_linearization_componentwise(name):
+    """one window alone (the latency path): every entry of r and J, the initial cost, and the 2 M control on the device's own export"""
+    w = lc.window(name)
+    bs, sms = solve_at_uploaded_state([w])
+    try:
+        assert sms[0].termination == 7
+        r, J = bs.export_jacobian(0)
+        check("device, %s:" % name, r, J, sms[0].initial_cost, nl.linearize(w))
+    finally:
+        bs.close()
+
+
+@gpu
+@needs_longdouble
+def test_device_batch_gives_the_single_windows_figures():
+    """33 windows in one BatchSolver (the batch kernels: k_eval_imu<true>, k_eval_ps<true, true>, k_eval_idp): windows 0 .. 5 distinct, the
+    rest copies of window 5.  Every judged window passes the rule; where its export is not the single window's bit for bit, both are held
+    to the referee (check does that) and the number of differing entries is printed."""
+    ws = [lc.window(n) for n in lc.BATCH_HEAD]
+    ws += [ws[-1].copy() for _ in range(lc.BATCH_N - len(ws))]
+    bs, sms = solve_at_uploaded_state(ws)
+    try:
+        assert all(s.termination == 7 for s in sms)
+        for i in list(range(len(lc.BATCH_HEAD))) + [lc.BATCH_N - 1]:
+            name = lc.BATCH_HEAD[min(i, len(lc.BATCH_HEAD) - 1)]
+            ref = nl.linearize(ws[i])
+            r, J = bs.export_jacobian(i)
+            check("device, batch window %d (%s):" % (i, name), r, J, sms[i].initial_cost, ref)
+            b1, s1 = solve_at_uploaded_state([ws[i]])
+            try:
+                r1, J1 = b1.export_jacobian(0)
+                check("device, %s alone:" % name, r1, J1, s1[0].initial_cost, ref)
+                print("   batch against single: %d entries of r, %d of J differ in bits; cost %s"
+                      % (int((r != r1).sum()), int((J != J1).sum()), "equal" if sms[i].initial_cost == s1[0].initial_cost else "differs"))
+            finally:
+                b1.close()
+    finally:
+        bs.close()
+
+
+@gpu
+@needs_longdouble
+@pytest.mark.parametrize("env", lc.KNOBS, ids=["-".join(e) for e in lc.KNOBS])
+def test_device_launch_knobs_componentwise(env, monkeypatch):
+    """the environment knobs that split the fused launches (read when the batch is created), on the three path windows"""
+    for k in ("SWF_NO_LAT_FUSE", "SWF_NO_STEP_FUSE", "SWF_NO_SPEC_EVAL", "SWF_NO_DECIDE_FUSE", "SWF_NO_COMP_FUSE"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for name in lc.PATH_WINDOWS:
+        w = lc.window(name)
+        bs, sms = solve_at_uploaded_state([w])
+        try:
+            assert sms[0].termination == 7
+            r, J = bs.export_jacobian(0)
+            check("device, %s, %s:" % (name, sorted(env)), r, J, sms[0].initial_cost, nl.linearize(w))
+        finally:
+            bs.close()
+
+
+def one_accepted_iteration(ws, strategy):
+    """(BatchSolver, summaries, the windows at the downloaded state) after a one-iteration solve"""
+    from rtk_visual_inertial_navigation_amd import solver
+    ws = [w.copy() for w in ws]
+    bs = solver.BatchSolver(ws)
+    sms = bs.solve(default_options(max_num_iterations=1, strategy=strategy))
+    return bs, sms, ws
+
+
+@gpu
+@needs_longdouble
+@pytest.mark.parametrize("strategy", [0, 1], ids=["dogleg", "lm"])
+@pytest.mark.parametrize("name", lc.STEP_WINDOWS)
+def test_device_after_one_accepted_iteration(name, strategy):
+    """A one-iteration solve whose step is accepted.  The engine (swf_batch_solve, csrc/swf_engine.hip) leaves the last linearisation at the
+    ACCEPTED point, which is the downloaded state: in the speculative dogleg flow the candidate is evaluated with its Jacobians (k_step_eval
+    on the latency path, the fused evaluation kernels otherwise) and k_decide makes it x; in the two-pass flow (Levenberg-Marquardt) the
+    candidate's cost comes from the cost-only kernels (k_step_eval<., false> / k_post_dogleg with d_eval_proj_cost, k_eval_idp<false>,
+    k_eval_prior<false>) and the accepted point is linearised again.  So both the reported cost and the export are held to the referee
+    at the downloaded state."""
+    bs, sms, ws = one_accepted_iteration([lc.window(name)], strategy)
+    try:
+        rows = sms[0].rows()
+        assert len(rows) == 2 and rows[1]["step_is_successful"], (name, rows)
+        ref = nl.linearize(ws[0])
+        r, J = bs.export_jacobian(0)
+        check("device, %s after one %s step:" % (name, ("dogleg", "LM")[strategy]), r, J, rows[1]["cost"], ref)
+    finally:
+        bs.close()
+
+
+@gpu
+@needs_longdouble
+def test_device_cost_only_kernels_of_a_large_batch():
+    """as many windows as the chip has CUs and more (260): the candidate IMU residuals leave the fused grid for k_eval_imu<false>
+    (cand_eval, csrc/swf_engine.hip); Levenberg-Marquardt, one accepted iteration, the reported cost against the longdouble cost at the
+    downloaded state.  Windows 0 and 1 are distinct, the rest copies of window 1."""
+    ws = [lc.window("imu_9"), lc.window("imu_1")]
+    ws += [ws[-1].copy() for _ in range(258)]
+    bs, sms, ws = one_accepted_iteration(ws, 1)
+    try:
+        for i in (0, 1, 259):
+            rows = sms[i].rows()
+            assert len(rows) == 2 and rows[1]["step_is_successful"], (i, rows)
+            ref = nl.linearize(ws[i])
+            c = cost_ratio(rows[1]["cost"], ref)
+            print("device, window %d of 260 after one LM step: cost %.3f brackets from the referee" % (i, c))
+            assert c <= M_COST, (i, c)
+    finally:
+        bs.close()
