@@ -29,6 +29,7 @@
 //   ImuIntegrate() + IMUProcess()               R/swf/swf_imu.cpp:117-213             -> swf_imu_frame_batch (ImuIntegrate below)
 //   initFramePoseByPnP() + solvePoseByPnP()     R/feature/feature_manager.cpp:164-243 -> swf_pnp_frame_batch (InitFramePoseByPnP below)
 //   rejectWithF() + undistortedPts() + ptsVelocity()  R/feature/feature_tracker.cpp:265-294, :334-376 -> swf_track_reject_batch (RejectWithF below)
+//   trackImage(): calcOpticalFlowPyrLK forward + reverse, the 0.5 px gate, inBorder   R/feature/feature_tracker.cpp:98-141 -> swf_klt_track_batch (TrackImageKLT below)
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
@@ -941,8 +942,8 @@ inline bool InitFramePoseByPnP(int frameCnt, V3 Ps[], M3 Rs[], const V3 tic[], c
 //   f_threshold, dt            F_THRESHOLD; cur_time - prev_time
 // Returns true on SWF_TRK_OK: out->status is then what cv::findFundamentalMat's status is to the reference, for ReduceVector below.
 // With fewer than 8 tracks (SWF_TRK_TOO_FEW, the reference skips the gate) or without a model it returns false and out->status is
-// empty; un_cur, un_prev and velocity are filled in all three cases.  KLT, setMask, goodFeaturesToTrack, the id maps and track_cnt stay
-// with the caller.
+// empty; un_cur, un_prev and velocity are filled in all three cases.  setMask, goodFeaturesToTrack, the id maps and track_cnt stay with
+// the caller; the KLT tracking in front of it is TrackImageKLT below.
 struct RejectWithFResult {
     int info = -1, n_inliers = 0, best = -1, n_iters = 0;
     std::vector<uint8_t> status;
@@ -969,6 +970,65 @@ inline bool RejectWithF(const Pts& cur_pts, const Pts& prev_pts, const double ca
     out->info = rc == SWF_OK ? info : -1; out->n_inliers = ok ? ni : 0; out->best = ok ? best : -1; out->n_iters = ok ? nit : 0;
     st.resize(ok ? (size_t)n : 0); out->status = st;
     out->un_cur.resize(lifted ? (size_t)n * 2 : 0); out->un_prev.resize(lifted ? (size_t)n * 2 : 0); out->velocity.resize(lifted ? (size_t)n * 2 : 0);
+    return ok;
+}
+
+// The sparse optical flow of the feature tracker: the tracking part of FeatureTracker::trackImage (R/feature/feature_tracker.cpp:98-141)
+// for one image pair on the device (swf_klt_track_batch with one pair and flag bit 0; a caller with many streams builds the same arrays
+// and makes one call).
+//   prev_img, cur_img          8-bit grey, rows x cols, dense rows (cv::Mat::data of a continuous CV_8UC1 image)
+//   prev_pts                   the tracker's vector of the previous positions (members x, y)
+//   predict_pts                the reference's hasPrediction branch (null: none): the forward pass starts from these positions with 1
+//                              pyramid level; when fewer than 10 points succeed it is run again without them with 3 levels, as there
+//   flow_back                  FLOW_BACK: the reverse pass from the previous positions with 1 level and the 0.5 px gate
+// Returns true when the call succeeded and the pair is SWF_KLT_OK: cur_pts holds the tracked positions, out->status is what the
+// reference's status is after the reverse check and inBorder, for ReduceVector below; out->why says which test dropped a point.
+// A non-finite position (SWF_KLT_BAD_INPUT) returns false with an empty status.  goodFeaturesToTrack, setMask, the id / track_cnt
+// bookkeeping, setPrediction itself and the stereo branch stay with the caller.
+struct TrackImageKLTResult {
+    int info = -1, n_keep = 0, levels = 0;              // levels: max_level of the forward pass that gave the result (1 or 3)
+    std::vector<uint8_t> status;
+    std::vector<int32_t> why;
+    std::vector<double> cur_px, back_px;                // [n][2]
+};
+template <class Pts>
+inline bool TrackImageKLT(const uint8_t* prev_img, const uint8_t* cur_img, int rows, int cols, const Pts& prev_pts, Pts* cur_pts,
+                          TrackImageKLTResult* out, const Pts* predict_pts = nullptr, bool flow_back = true) {
+    if (!out || !cur_pts || (predict_pts && predict_pts->size() != prev_pts.size())) return false;
+    const int32_t n = (int32_t)prev_pts.size(), first[2] = { 0, n };
+    std::vector<double> p((size_t)(n + 1) * 2, 0.0), g((size_t)(n + 1) * 2, 0.0);
+    for (int32_t i = 0; i < n; i++) {
+        p[(size_t)i * 2] = prev_pts[(size_t)i].x; p[(size_t)i * 2 + 1] = prev_pts[(size_t)i].y;
+        if (predict_pts) { g[(size_t)i * 2] = (*predict_pts)[(size_t)i].x; g[(size_t)i * 2 + 1] = (*predict_pts)[(size_t)i].y; }
+    }
+    std::vector<uint8_t> st((size_t)n + 1, 0);
+    std::vector<int32_t> why((size_t)n + 1, 0);
+    out->cur_px.assign((size_t)(n + 1) * 2, 0.0); out->back_px.assign((size_t)(n + 1) * 2, 0.0);
+    int32_t info = -1, nk = 0;
+    int rc = SWF_OK, levels = 3;
+    bool done = false;
+    if (predict_pts) {
+        levels = 1;
+        rc = swf_klt_track_batch(1, rows, cols, prev_img, cur_img, first, p.data(), g.data(), 21, 1, 1, 30, 0.01, 1e-4, 0.5, 1 | 2 | (flow_back ? 4 : 0),
+                                 out->cur_px.data(), out->back_px.data(), st.data(), why.data(), nullptr, &nk, &info, nullptr, nullptr, nullptr, 0, nullptr);
+        int succ = 0;
+        for (int32_t i = 0; i < n; i++) succ += why[(size_t)i] != SWF_KLT_FWD_LOST && why[(size_t)i] != SWF_KLT_FWD_FLAT;
+        done = rc != SWF_OK || info != SWF_KLT_OK || succ >= 10;
+    }
+    if (!done) {
+        levels = 3;
+        rc = swf_klt_track_batch(1, rows, cols, prev_img, cur_img, first, p.data(), nullptr, 21, 3, 1, 30, 0.01, 1e-4, 0.5, 1 | (flow_back ? 4 : 0),
+                                 out->cur_px.data(), out->back_px.data(), st.data(), why.data(), nullptr, &nk, &info, nullptr, nullptr, nullptr, 0, nullptr);
+    }
+    const bool ok = rc == SWF_OK && info == SWF_KLT_OK;
+    out->info = rc == SWF_OK ? info : -1; out->n_keep = ok ? nk : 0; out->levels = levels;
+    st.resize(ok ? (size_t)n : 0); why.resize(ok ? (size_t)n : 0);
+    out->status = st; out->why = why;
+    out->cur_px.resize(ok ? (size_t)n * 2 : 0); out->back_px.resize(ok && flow_back ? (size_t)n * 2 : 0);
+    if (ok) {
+        cur_pts->resize((size_t)n);
+        for (int32_t i = 0; i < n; i++) { (*cur_pts)[(size_t)i].x = (float)out->cur_px[(size_t)i * 2]; (*cur_pts)[(size_t)i].y = (float)out->cur_px[(size_t)i * 2 + 1]; }
+    }
     return ok;
 }
 

@@ -20,6 +20,7 @@
 #ifndef SWF_SOLVER_H
 #define SWF_SOLVER_H
 
+#include <stddef.h>
 #include <stdint.h>
 #include "swf_types.h"
 
@@ -712,6 +713,82 @@ int swf_track_reject_batch(int32_t n_pairs, const int32_t* first, const double* 
                            double confidence, uint64_t seed, int32_t flags, uint8_t* status, int32_t* keep_idx, int32_t* n_inliers,
                            int32_t* best, int32_t* n_iters, int32_t* info, double* F, double* un_cur, double* un_prev,
                            double* velocity, int32_t* samples, double* hyp, int32_t* count, int32_t on_device, void* stream);
+
+/* Input producer: the tracked pixel pairs themselves — the sparse optical flow of FeatureTracker::trackImage
+ * (R/feature/feature_tracker.cpp:98-141) for n_pairs independent image pairs, one wavefront per point: a forward pyramidal
+ * Lucas-Kanade pass (cv::calcOpticalFlowPyrLK, 21 x 21, 3 levels), a reverse pass with 1 level started from the previous positions
+ * (FLOW_BACK), the 0.5 px forward-backward gate, inBorder and reduceVector.  It is OpenCV's LKTrackerInvoker restated, with one
+ * declared difference: OpenCV accumulates A and b in float in SIMD order; here they are exact integer sums converted once to double,
+ * so the float64 referee of the tests is met bit for bit.  Not here: goodFeaturesToTrack, setMask, the id / track_cnt bookkeeping,
+ * setPrediction, the stereo branch.  The specification; positions are (x, y), floor is towards -inf, rint to nearest even,
+ * descale(v, n) = (v + 2^(n-1)) >> n arithmetically, r101(i, n) = |i|, and 2 (n - 1) - i above n - 1:
+ *   pyramid    level l + 1 has size ((w + 1) / 2, (h + 1) / 2); dst(x, y) = (sum_ij k_i k_j src(r101(2x + i - 2, w), r101(2y + j - 2, h))
+ *              + 128) >> 8, k = 1 4 6 4 1.  Building stops before a level whose width or height would be <= win; the level count
+ *              used is min(max_level, that), for the reverse pass min(back_level, that).
+ *   Scharr     inside the image Ix(x, y) = 3 (P(x+1, y-1) - P(x-1, y-1)) + 10 (P(x+1, y) - P(x-1, y)) + 3 (P(x+1, y+1) - P(x-1, y+1)), P
+ *              through r101, Iy the transposed stencil; both 0 outside the image.  Intensities outside are read through r101.
+ *   weights    at p: ip = floor(p), a = p.x - ip.x, b = p.y - ip.y, w00 = rint((1-a)(1-b) 16384), w01 = rint(a (1-b) 16384),
+ *              w10 = rint((1-a) b 16384), w11 = 16384 - w00 - w01 - w10 (each product rounded once, left to right); for a source S
+ *              and the win^2 offsets (i, j): v = S(ip+(i,j)) w00 + S(ip+(i+1,j)) w01 + S(ip+(i,j+1)) w10 + S(ip+(i+1,j+1)) w11.
+ *              p is outside its level when ip.x < -win or ip.x >= cols_l, or the same in y.
+ *   per point  for l = top .. 0, half = (win - 1) / 2, template image I, search image J:
+ *              1. p = prev 2^-l; q = (l == top) ? (bit 1 ? guess : prev) 2^-l : 2 q; p -= half; p outside: LOST at level 0, else the
+ *                 next level with q kept.
+ *              2. It = descale(v_I, 9), Itx = descale(v_Ix, 14), Ity alike; A11 = (sum Itx^2) 2^-20, A12 = (sum Itx Ity) 2^-20,
+ *                 A22 = (sum Ity^2) 2^-20; D = A11 A22 - A12 A12; minEig = (A22 + A11 - sqrt((A11 - A22)(A11 - A22) + 4 A12 A12)) /
+ *                 (2 win^2); minEig < min_eig or D < 2^-23: FLAT at level 0, else the next level; D = 1 / D.
+ *              3. q -= half; for j = 0 .. max_count - 1: q outside: LOST at level 0, break; d = descale(v_J at q, 9) - It;
+ *                 b1 = (sum d Itx) 2^-20, b2 alike; delta = ((A12 b2 - A22 b1) D, (A12 b1 - A11 b2) D); q += delta, the iteration
+ *                 counts; |delta|^2 <= eps^2: break; j > 0 and |delta + previous delta| < 0.01 in x and in y: q -= 0.5 delta, break.
+ *                 Then q += half.
+ *              4. cur = q of level 0.  The reverse pass: the same with the images swapped, prev := cur, the initial flow the original
+ *                 prev_px, over the reverse level count; it gives back.  BACK_FAR: sqrt(dx^2 + dy^2) > back_dist, (dx, dy) = prev - back.
+ *                 BORDER: !(1 <= rint(cur.x) < cols - 1 and 1 <= rint(cur.y) < rows - 1).  The reverse pass runs for every point,
+ *                 whatever the forward pass found (as in the reference).
+ *   exactness  |It| <= 8160, |Itx| <= 4080: every sum over 441 terms is an integer below 2^35, exact in any order; everything else
+ *              is a fixed sequence of double operations, each rounded once (no contraction, correctly rounded sqrt and division).
+ * Arrays:
+ *   prev_img, cur_img [n_pairs][rows][cols]  8-bit grey, dense rows
+ *   first      [n_pairs + 1]                 point offsets
+ *   prev_px, guess_px, cur_px, back_px [first[n_pairs]][2];  guess_px goes with flag bit 1 and only with it (else null)
+ *   win, max_level, back_level, max_count, eps, min_eig, back_dist: the reference's 21, 3, 1, 30, 0.01, 1e-4, 0.5;  max_count 1 .. 1000
+ *   flags      bit 0: round prev_px / guess_px on entry and cur_px / back_px at the end of each pass through float, where the reference
+ *              holds a cv::Point2f (everything between is double);  bit 1: guess_px is the initial flow of the forward pass
+ *              (hasPrediction);  bit 2: run the reverse pass and its gate (FLOW_BACK).  The reference: 5.
+ *   status     [..] 1 = keep;  why [..] the first of the point codes that applies, in the order of the enum (without bit 2 the BACK codes
+ *              do not occur and back_px is not written)
+ *   keep_idx   [..], n_keep [n_pairs]        as in swf_track_reject_batch: ascending indices from first[k], -1 behind them
+ *   trace_iters [..][2][SWF_KLT_LMAX + 1]    iterations run per pass (0 forward, 1 reverse) and level; -1: level not visited, the
+ *              template window outside the level, or the level flat
+ *   trace_px   [..][2][SWF_KLT_LMAX + 1][2]  q after that level in that level's pixels (as set in step 1 where the level was left
+ *              early; 0 for a level not visited)
+ *   pyr        [n_pairs][swf_klt_pyramid_bytes(rows, cols, max(max_level, back_level))]  the workspace and a stage export: per pair
+ *              the levels 1 .. of prev, then (from half of the pair's bytes) of cur, dense; the layout depends on the image size alone,
+ *              levels that are not built (see pyramid) are not written.  Host memory: may be null (staged internally).  Device
+ *              memory: required, and written for every pair.
+ * Every output but info may be null; in device memory n_keep needs one of status, why and keep_idx, which carries the flags
+ * between the kernels (SWF_E_INVALID otherwise).
+ * info: SWF_KLT_BAD_INPUT (a non-finite point or guess, tested on what is staged): the pair writes its info only.  rows or cols <= win
+ * or > 8192, an even win or one outside 3 .. 21, a level outside 0 .. 4, max_count outside 1 .. 1000, unknown flag bits, more than 2^20
+ * pairs, (host memory) a pair above SWF_KLT_NMAX points: SWF_E_UNSUPPORTED; null required pointers, guess_px without bit 1 or bit 1
+ * without it, (host memory) a negative or decreasing `first`, eps, min_eig or back_dist not finite and positive: SWF_E_INVALID.  With host
+ * memory the BAD_INPUT pairs are found before the device is touched, and a call none of whose pairs has a point to track does not
+ * touch it at all.  Device memory: a pair whose offsets are negative, decreasing or above SWF_KLT_NMAX reports info = -1 and writes
+ * nothing else.  A pair's result does not depend on the other pairs of the call, and a rerun gives the same bits.  on_device as for
+ * swf_preintegrate_batch.  max(max_level, back_level) + 2 launches on the caller's stream. */
+enum { SWF_KLT_OK = 0, SWF_KLT_BAD_INPUT = 1 };                      /* per pair */
+enum { SWF_KLT_TRACKED = 0, SWF_KLT_FWD_LOST = 1, SWF_KLT_FWD_FLAT = 2, SWF_KLT_BACK_LOST = 3, SWF_KLT_BACK_FLAT = 4,
+       SWF_KLT_BACK_FAR = 5, SWF_KLT_BORDER = 6 };                  /* per point: why */
+#define SWF_KLT_WMAX 21     /* window side, odd, 3 .. 21 */
+#define SWF_KLT_LMAX 4      /* max_level, back_level: 0 .. 4 */
+#define SWF_KLT_NMAX 4096   /* points per pair */
+size_t swf_klt_pyramid_bytes(int32_t rows, int32_t cols, int32_t max_level);      /* host only: workspace per PAIR (both images, levels 1 ..) */
+int swf_klt_track_batch(int32_t n_pairs, int32_t rows, int32_t cols, const uint8_t* prev_img, const uint8_t* cur_img,
+                        const int32_t* first, const double* prev_px, const double* guess_px,
+                        int32_t win, int32_t max_level, int32_t back_level, int32_t max_count, double eps, double min_eig,
+                        double back_dist, int32_t flags,
+                        double* cur_px, double* back_px, uint8_t* status, int32_t* why, int32_t* keep_idx, int32_t* n_keep,
+                        int32_t* info, int32_t* trace_iters, double* trace_px, uint8_t* pyr, int32_t on_device, void* stream);
 
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).

@@ -65,6 +65,7 @@ EXPORTED = [
     "swf_imu_frame_batch", "swf_preintegrate_runs_batch",
     "swf_pnp_frame_batch",
     "swf_track_reject_batch",
+    "swf_klt_track_batch", "swf_klt_pyramid_bytes",
 ]
 
 
@@ -1018,6 +1019,73 @@ def track_reject_batch(cur_px, prev_px, cam, dt, col=752, row=480, focal=1000.0,
                                       C.c_int32(0), None), "track_reject_batch")
     for key in ("status", "keep_idx", "un_cur", "un_prev", "velocity"):
         out[key] = out[key][:tot]
+    return out
+
+
+KLT_OK, KLT_BAD_INPUT = 0, 1
+KLT_TRACKED, KLT_FWD_LOST, KLT_FWD_FLAT, KLT_BACK_LOST, KLT_BACK_FLAT, KLT_BACK_FAR, KLT_BORDER = 0, 1, 2, 3, 4, 5, 6
+KLT_WMAX, KLT_LMAX, KLT_NMAX = 21, 4, 4096
+
+
+def klt_pyramid_bytes(rows, cols, max_level):
+    """swf_klt_pyramid_bytes: the pyramid workspace of one pair (both images, levels 1 .. max_level)"""
+    fn = lib().swf_klt_pyramid_bytes
+    fn.restype = C.c_size_t
+    return int(fn(C.c_int32(rows), C.c_int32(cols), C.c_int32(max_level)))
+
+
+def klt_track_batch(prev_img, cur_img, prev_px, guess_px=None, win=21, max_level=3, back_level=1, max_count=30, eps=0.01, min_eig=1e-4,
+                    back_dist=0.5, flags=5, fill=0.0, stages=False):
+    """The sparse optical flow of FeatureTracker::trackImage (R/feature/feature_tracker.cpp:98-141) for a batch of image pairs on the
+    device (swf_klt_track_batch): forward pyramidal Lucas-Kanade, the reverse pass, the forward-backward gate and inBorder.  prev_img,
+    cur_img: [n][rows][cols] uint8; prev_px (and guess_px, with flag bit 1): lists of [n_k][2] pixel positions (x, y); flags bit 0:
+    round through float where the reference holds a cv::Point2f, bit 1: guess_px is the initial flow, bit 2: the reverse pass and its
+    gate.  Returns dict(cur_px, back_px, status, why, keep_idx, first, n_keep, info) and, with stages=True, trace_iters [..][2][5],
+    trace_px [..][2][5][2] and pyr [n][klt_pyramid_bytes(rows, cols, max(max_level, back_level))]; the per-point arrays are
+    [first[n]], pair k owning first[k] .. first[k + 1].  A pair whose info is KLT_BAD_INPUT leaves its outputs at `fill` (the integer
+    outputs at int(fill), status at 255, pyr at 0)."""
+    pimg = np.ascontiguousarray(prev_img, dtype=np.uint8)
+    cimg = np.ascontiguousarray(cur_img, dtype=np.uint8)
+    if pimg.ndim != 3 or pimg.shape != cimg.shape:
+        raise SwfError("klt_track_batch: the images must be two [n][rows][cols] arrays of one shape")
+    n, rows, cols = pimg.shape
+    pp = [np.asarray(p, np.float64).reshape(-1, 2) for p in prev_px]
+    if len(pp) != n:
+        raise SwfError("klt_track_batch: %d image pairs and %d point sets" % (n, len(pp)))
+    first = np.zeros(n + 1, np.int32)
+    for i in range(n):
+        first[i + 1] = first[i] + pp[i].shape[0]
+    tot = int(first[n])
+    fp = np.ascontiguousarray(np.concatenate(pp + [np.zeros((1, 2))]))
+    fg = None
+    if guess_px is not None:
+        gp = [np.asarray(p, np.float64).reshape(-1, 2) for p in guess_px]
+        if [g.shape for g in gp] != [p.shape for p in pp]:
+            raise SwfError("klt_track_batch: guess_px does not match prev_px")
+        fg = np.ascontiguousarray(np.concatenate(gp + [np.zeros((1, 2))]))
+    pts = max(tot, 1)
+    T = KLT_LMAX + 1
+    out = dict(cur_px=np.full((pts, 2), float(fill)), back_px=np.full((pts, 2), float(fill)), status=np.full(pts, 255, np.uint8),
+               why=np.full(pts, int(fill), np.int32), keep_idx=np.full(pts, int(fill), np.int32), first=first,
+               n_keep=np.full(n, int(fill), np.int32), info=np.full(n, -1, np.int32))
+    pi, pb = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    ex = [None, None, None]
+    if stages:
+        nb = klt_pyramid_bytes(rows, cols, max(min(max(max_level, back_level), KLT_LMAX), 0))
+        out.update(trace_iters=np.full((pts, 2, T), int(fill), np.int32), trace_px=np.full((pts, 2, T, 2), float(fill)),
+                   pyr=np.zeros((n, max(nb, 1)), np.uint8))
+        ex = [out["trace_iters"].ctypes.data_as(pi), out["trace_px"].ctypes.data_as(_pd), out["pyr"].ctypes.data_as(pb)]
+    _chk(lib().swf_klt_track_batch(C.c_int32(n), C.c_int32(rows), C.c_int32(cols), pimg.ctypes.data_as(pb), cimg.ctypes.data_as(pb),
+                                   first.ctypes.data_as(pi), fp.ctypes.data_as(_pd), fg.ctypes.data_as(_pd) if fg is not None else None,
+                                   C.c_int32(win), C.c_int32(max_level), C.c_int32(back_level), C.c_int32(max_count), C.c_double(eps),
+                                   C.c_double(min_eig), C.c_double(back_dist), C.c_int32(flags), out["cur_px"].ctypes.data_as(_pd),
+                                   out["back_px"].ctypes.data_as(_pd), out["status"].ctypes.data_as(pb), out["why"].ctypes.data_as(pi),
+                                   out["keep_idx"].ctypes.data_as(pi), out["n_keep"].ctypes.data_as(pi), out["info"].ctypes.data_as(pi),
+                                   ex[0], ex[1], ex[2], C.c_int32(0), None), "klt_track_batch")
+    for key in ("cur_px", "back_px", "status", "why", "keep_idx") + (("trace_iters", "trace_px") if stages else ()):
+        out[key] = out[key][:tot]
+    if stages:
+        out["pyr"] = out["pyr"][:, :nb]
     return out
 
 

@@ -1,0 +1,283 @@
+"""Batched pyramidal Lucas-Kanade tracking (swf_klt_track_batch / solver.klt_track_batch / swf_ceres::TrackImageKLT), the part
+that needs no GPU: the exported symbols, the host-side rejections, the numpy referee of tests/np_klt.py against independent
+restatements of its pyramid and its derivatives, the exactness of its sums, a golden file of its results, its accuracy against a known
+flow, the compiled host loop of tests/perf/klt_host.cpp against it bit for bit, and the conditions on the test inputs that
+tests/test_klt_gpu.py relies on."""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import klt_cases as kc
+import klt_gen as kg
+import np_klt as nk
+from rtk_visual_inertial_navigation_amd import build, solver
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "klt_referee.json")
+E_INVALID, E_UNSUPPORTED = -2, -3
+SENTINEL = -7.0
+pi = C.POINTER(C.c_int32)
+pd = C.POINTER(C.c_double)
+pb = C.POINTER(C.c_uint8)
+OUT_KEYS = ("cur_px", "back_px", "status", "why", "keep_idx", "n_keep", "info", "trace_iters", "trace_px", "pyr")
+KIND = dict(cur_px=pd, back_px=pd, status=pb, why=pi, keep_idx=pi, n_keep=pi, info=pi, trace_iters=pi, trace_px=pd, pyr=pb)
+
+
+def test_klt_symbol_exported():
+    build.build()
+    lib = C.CDLL(solver.LIB_PATH)
+    assert hasattr(lib, "swf_klt_track_batch") and hasattr(lib, "swf_klt_pyramid_bytes")
+    assert "swf_klt_track_batch" in solver.EXPORTED and "swf_klt_pyramid_bytes" in solver.EXPORTED and callable(solver.klt_track_batch)
+    hdr = open(os.path.join(ROOT, "include", "swf_solver.h")).read()
+    for s in ("int swf_klt_track_batch(", "size_t swf_klt_pyramid_bytes(", "SWF_KLT_OK = 0, SWF_KLT_BAD_INPUT = 1", "SWF_KLT_TRACKED = 0",
+              "SWF_KLT_FWD_LOST = 1", "SWF_KLT_FWD_FLAT = 2", "SWF_KLT_BACK_LOST = 3", "SWF_KLT_BACK_FLAT = 4", "SWF_KLT_BACK_FAR = 5",
+              "SWF_KLT_BORDER = 6", "#define SWF_KLT_WMAX 21", "#define SWF_KLT_LMAX 4", "#define SWF_KLT_NMAX 4096"):
+        assert s in hdr, s
+    assert "TrackImageKLT(" in open(os.path.join(ROOT, "include", "swf_ceres.hpp")).read()
+    assert (solver.KLT_OK, solver.KLT_BAD_INPUT) == (nk.OK, nk.BAD_INPUT)
+    assert (solver.KLT_TRACKED, solver.KLT_FWD_LOST, solver.KLT_FWD_FLAT, solver.KLT_BACK_LOST, solver.KLT_BACK_FLAT, solver.KLT_BACK_FAR,
+            solver.KLT_BORDER) == (nk.TRACKED, nk.FWD_LOST, nk.FWD_FLAT, nk.BACK_LOST, nk.BACK_FLAT, nk.BACK_FAR, nk.BORDER)
+    assert (solver.KLT_WMAX, solver.KLT_LMAX, solver.KLT_NMAX) == (nk.WMAX, nk.LMAX, nk.NMAX)
+    assert lib.swf_version() == 112
+    for rows, cols, lv in ((96, 128, 3), (480, 752, 3), (45, 47, 1), (24, 31, 4), (177, 201, 0)):
+        assert solver.klt_pyramid_bytes(rows, cols, lv) == nk.pyramid_bytes(rows, cols, lv)
+    assert solver.klt_pyramid_bytes(96, 128, 5) == 0 and solver.klt_pyramid_bytes(0, 128, 1) == 0
+
+
+def _raw_call(pts_list, drop=None, first=None, n=None, rows=96, cols=128, guess=None, **kw):
+    """swf_klt_track_batch on host memory with every output pre-filled; returns (code, outputs)"""
+    a = dict(nk.DEFAULTS)
+    a.update(kw)
+    nf = len(pts_list)
+    fst = np.concatenate([[0], np.cumsum([p.shape[0] for p in pts_list])]).astype(np.int32) if first is None else np.asarray(first, np.int32)
+    fp = np.ascontiguousarray(np.concatenate(list(pts_list) + [np.zeros((1, 2))]))
+    fg = None if guess is None else np.ascontiguousarray(np.concatenate(list(guess) + [np.zeros((1, 2))]))
+    N = fp.shape[0]
+    img = np.full((max(nf, 1), max(rows, 1), max(cols, 1)), 100, np.uint8)
+    o = dict(cur_px=np.full((N, 2), SENTINEL), back_px=np.full((N, 2), SENTINEL), status=np.full(N, 77, np.uint8), why=np.full(N, -9, np.int32),
+             keep_idx=np.full(N, -9, np.int32), n_keep=np.full(max(nf, 1), -9, np.int32), info=np.full(max(nf, 1), -9, np.int32),
+             trace_iters=np.full((N, 2, 5), -9, np.int32), trace_px=np.full((N, 2, 5, 2), SENTINEL), pyr=np.full((max(nf, 1), 1 << 14), 77, np.uint8))
+    p = {k: o[k].ctypes.data_as(KIND[k]) for k in OUT_KEYS}
+    p.update(prev=img.ctypes.data_as(pb), cur=img.ctypes.data_as(pb), first=fst.ctypes.data_as(pi), pts=fp.ctypes.data_as(pd),
+             guess=None if fg is None else fg.ctypes.data_as(pd))
+    if drop:
+        p[drop] = None
+    rc = solver.lib().swf_klt_track_batch(C.c_int32(nf if n is None else n), C.c_int32(rows), C.c_int32(cols), p["prev"], p["cur"], p["first"], p["pts"],
+                                          p["guess"], C.c_int32(a["win"]), C.c_int32(a["max_level"]), C.c_int32(a["back_level"]),
+                                          C.c_int32(a["max_count"]), C.c_double(a["eps"]), C.c_double(a["min_eig"]), C.c_double(a["back_dist"]),
+                                          C.c_int32(a["flags"]), *[p[k] for k in OUT_KEYS], C.c_int32(0), None)
+    return rc, o
+
+
+def _untouched(o, info=False):
+    return ((o["status"] == 77).all() and (o["pyr"] == 77).all() and all((o[k] == SENTINEL).all() for k in ("cur_px", "back_px", "trace_px"))
+            and all((o[k] == -9).all() for k in ("why", "keep_idx", "n_keep", "trace_iters") + (("info",) if info else ())))
+
+
+def test_host_side_validation_needs_no_device():
+    """A call whose pairs are all BAD_INPUT returns SWF_OK with that code and nothing else written, without touching the device, so this
+    runs anywhere; so does a call without a point (n_keep = 0 is the host's).  The argument errors return their codes and write nothing."""
+    build.build()
+    rng = np.random.default_rng(1)
+    bad = [rng.uniform(20, 70, (n, 2)) for n in (3, 9, 64)]
+    bad[0][1, 0] = np.nan; bad[1][8, 1] = np.inf; bad[2][0, 0] = 1e39          # the last: finite as a double, infinite as a float
+    rc, o = _raw_call(bad)
+    assert rc == 0, solver.lib().swf_last_error()
+    assert o["info"][:3].tolist() == [nk.BAD_INPUT] * 3 and _untouched(o)
+    good = [rng.uniform(20, 70, (n, 2)) for n in (3, 9)]
+    g = [p.copy() for p in good]; g[0][0, 1] = np.nan; g[1][2, 0] = -np.inf
+    rc, o = _raw_call(good, guess=g, flags=7)                                   # non-finite guesses
+    assert rc == 0 and o["info"].tolist() == [nk.BAD_INPUT] * 2 and _untouched(o)
+    rc2, o2 = _raw_call([np.zeros((0, 2)), bad[0]])
+    assert rc2 == 0 and o2["info"].tolist() == [nk.OK, nk.BAD_INPUT] and o2["n_keep"].tolist() == [0, -9]
+    res = solver.klt_track_batch(np.zeros((3, 96, 128), np.uint8), np.zeros((3, 96, 128), np.uint8), bad, fill=SENTINEL, stages=True)
+    assert res["info"].tolist() == [nk.BAD_INPUT] * 3 and (res["cur_px"] == SENTINEL).all() and (res["trace_px"] == SENTINEL).all()
+    for drop in ("prev", "cur", "first", "pts", "info"):
+        rc, o = _raw_call(bad, drop=drop)
+        assert rc == E_INVALID and _untouched(o, info=True), drop
+    for drop in OUT_KEYS:                                                       # optional, all of them but info
+        if drop != "info":
+            rc, o = _raw_call(bad, drop=drop)
+            assert rc == 0 and _untouched(o), drop
+    for first in ([0, 3, 12, 11], [-1, 3, 12, 76]):
+        rc, o = _raw_call(bad, first=first)
+        assert rc == E_INVALID and _untouched(o, info=True), first
+    rc, o = _raw_call(bad, n=-1)
+    assert rc == E_INVALID and _untouched(o, info=True)
+    for kw in (dict(flags=7), dict(guess=bad, flags=5)):                        # bit 1 without guess_px, guess_px without bit 1
+        rc, o = _raw_call(bad, **kw)
+        assert rc == E_INVALID and _untouched(o, info=True), kw
+    for key in ("eps", "min_eig", "back_dist"):
+        for v in (0.0, -1.0, np.nan, np.inf):
+            rc, o = _raw_call(bad, **{key: v})
+            assert rc == E_INVALID and _untouched(o, info=True), (key, v)
+    for kw in (dict(win=20), dict(win=1), dict(win=23), dict(rows=21), dict(cols=21), dict(rows=8193), dict(cols=8193), dict(max_level=-1),
+               dict(max_level=5), dict(back_level=-1), dict(back_level=5), dict(max_count=0), dict(max_count=1001), dict(flags=8), dict(flags=-4),
+               dict(first=[0, 3, 12, 12 + nk.NMAX + 1])):
+        rc, o = _raw_call(bad, **kw)
+        assert rc == E_UNSUPPORTED and _untouched(o, info=True), kw
+    assert b"swf_klt_track_batch" in solver.lib().swf_last_error()
+    rc, o = _raw_call([], n=0)
+    assert rc == 0 and _untouched(o, info=True)
+
+
+def _pyr_down_direct(src):
+    """the 5 x 5 stencil written out pixel by pixel, with its own reflection"""
+    h, w = src.shape
+    k = [1, 4, 6, 4, 1]
+
+    def refl(i, n):
+        i = -i if i < 0 else i
+        return 2 * (n - 1) - i if i > n - 1 else i
+    out = np.zeros(((h + 1) // 2, (w + 1) // 2), np.uint8)
+    for y in range(out.shape[0]):
+        for x in range(out.shape[1]):
+            s = 0
+            for j in range(5):
+                for i in range(5):
+                    s += k[i] * k[j] * int(src[refl(2 * y + j - 2, h), refl(2 * x + i - 2, w)])
+            out[y, x] = (s + 128) >> 8
+    return out
+
+
+def test_pyramid_referee_against_a_direct_restatement():
+    for h, w in ((45, 47), (24, 31), (22, 23)):
+        img = kg.tex(h, w, 0.3, 0.1, h)
+        assert np.array_equal(nk.pyr_down(img), _pyr_down_direct(img)), (h, w)
+    flat = np.full((33, 37), 201, np.uint8)
+    assert (nk.pyr_down(flat) == 201).all()                                      # the kernel sums to 256
+    assert [lv.shape for lv in nk.pyramid(kg.tex(96, 128, 0, 0, 1), 21, 3)] == [(96, 128), (48, 64), (24, 32)]
+    assert [lv.shape for lv in nk.pyramid(kg.tex(45, 47, 0, 0, 1), 21, 3)] == [(45, 47), (23, 24)]
+    assert nk.level_sizes(24, 31, 5, 4) == [(24, 31), (12, 16), (6, 8)]
+
+
+def test_scharr_against_a_second_formulation():
+    """the separable form (smoothing 3 10 3 across, difference -1 0 1 along) on a reflect-101 padded copy, and 0 outside the image"""
+    img = kg.tex(30, 41, 0.0, 0.0, 5)
+    h, w = img.shape
+    P = np.pad(img.astype(np.int64), 1, mode="reflect")
+    ix = 3 * (P[:-2, 2:] - P[:-2, :-2]) + 10 * (P[1:-1, 2:] - P[1:-1, :-2]) + 3 * (P[2:, 2:] - P[2:, :-2])
+    sm = 3 * P[:, :-2] + 10 * P[:, 1:-1] + 3 * P[:, 2:]
+    iy = sm[2:] - sm[:-2]
+    ys, xs = np.arange(-4, h + 4), np.arange(-4, w + 4)
+    gx, gy = nk.scharr(img, ys, xs)
+    assert np.array_equal(gx[4:-4, 4:-4], ix) and np.array_equal(gy[4:-4, 4:-4], iy)
+    mask = np.ones(gx.shape, bool); mask[4:-4, 4:-4] = False
+    assert (gx[mask] == 0).all() and (gy[mask] == 0).all() and np.abs(ix).max() <= 4080 and np.abs(iy).max() <= 4080
+
+
+def test_sums_are_exact_in_any_order():
+    """every sum the referee forms is a sum of integers far below 2^53: summing the terms as doubles in reversed order gives the same bits"""
+    sums = []
+    c = kc.edge_cases()[0]
+    nk.track_pair(c["prev"], c["cur"], c["pts"], sums=sums)
+    white = np.zeros((96, 128), np.uint8); white[::2, ::2] = 255                  # the largest derivatives an image can have
+    nk.track_pair(white, np.roll(white, 1, 1), kg.points(96, 128, 8, 16, 3), sums=sums)
+    assert len(sums) > 1000
+    top = 0
+    for terms in sums:
+        t = terms.ravel().astype(np.float64)
+        fwd = rev = 0.0
+        for v in t:
+            fwd += v
+        for v in t[::-1]:
+            rev += v
+        assert fwd == rev == float(int(terms.sum()))
+        top = max(top, abs(int(terms.sum())), int(np.abs(terms).sum()))
+    assert top < 2 ** 35 < 2 ** 53
+
+
+def _golden_now():
+    c = kc.count_cases()[2]                                                       # 96 x 128, 65 points
+    ref = kc.referee("count")[2]
+    lv = ref["levels"]
+    return dict(case="klt_cases.count_cases()[2]", level_sizes=[list(a.shape) for a in lv[:len(lv) // 2]], pyramid_crc=[nk.crc(a) for a in lv],
+                cur_px=[[float(v).hex() for v in p] for p in ref["cur_px"]], why=ref["why"].tolist(), trace_iters=ref["trace_iters"].tolist(),
+                inputs_crc=[nk.crc(c["prev"]), nk.crc(c["cur"]), nk.crc(c["pts"])])
+
+
+def test_golden_referee_results():
+    """the level sizes, a CRC of every pyramid level (prev, then cur) and cur_px, why and trace_iters of one 96 x 128 case as recorded: a
+    change of the referee or of the generator shows here, not as a silent change of what the device is held to"""
+    want = json.load(open(GOLDEN))
+    assert _golden_now() == want
+
+
+def test_truth():
+    """The referee against the known flow, the four cases of klt_gen.TRUTH with 64 points and the reference defaults: every point is kept
+    and |cur - prev - shift| <= 0.5 px, the reference's own forward-backward gate.  Measured with this generator: 64 of 64 kept in all
+    four cases, largest errors 0.028, 0.018, 0.018 and 0 px."""
+    for c, ref in zip(kc.truth_cases(), kc.referee("truth")):
+        err = np.abs(ref["cur_px"] - c["pts"] - np.array(c["shift"])).max()
+        print(c["name"], "kept", ref["n_keep"], "largest error %.4f px" % err)
+        assert len(nk.level_sizes(*c["prev"].shape, 21, 3)) - 1 == c["levels"]
+        assert ref["info"] == nk.OK and ref["n_keep"] == 64 and (ref["status"] == 1).all() and err <= 0.5
+
+
+def test_cases_reach_every_code_and_branch():
+    """what tests/test_klt_gpu.py relies on: the edge cases reach every `why` code, the traces hold skipped levels (-1 below the top) and
+    runs that end by the iteration limit, by eps and at once, and the prediction case starts away from the previous positions"""
+    refs = kc.referee("edge")
+    seen = set()
+    for r in refs:
+        seen |= set(r["why"].tolist())
+    assert seen == {nk.TRACKED, nk.FWD_LOST, nk.FWD_FLAT, nk.BACK_LOST, nk.BACK_FLAT, nk.BACK_FAR, nk.BORDER}
+    it = np.concatenate([r["trace_iters"].reshape(-1, 5) for r in refs])
+    assert (it[:, :3] == 30).any() and (it[:, :3] == 1).any() and (it[:, :3] == 0).any() and (it[:, 0] == -1).any() and (it[:, 3:] == -1).all()
+    opt = {c["name"]: r for c, r in zip(kc.option_cases(), kc.referee("option"))}
+    assert (opt["count1"]["trace_iters"][:, :, :3].max() == 1) and (opt["back0"]["trace_iters"][:, 1, 1:] == -1).all()
+    assert (opt["back_above"]["trace_iters"][:, 0, 1:] == -1).all() and (opt["back_above"]["trace_iters"][:, 1, 2] >= 0).all()
+    assert (opt["no_back"]["trace_iters"][:, 1] == -1).all() and not np.array_equal(opt["win5"]["cur_px"], opt["win11"]["cur_px"])
+    g = kc.option_cases()[0]
+    assert g["args"]["flags"] & 2 and np.abs(g["guess"] - g["pts"]).min() > 1.0 and opt["guess"]["n_keep"] == 40
+    assert [r["info"] for r in kc.referee("ragged")].count(nk.BAD_INPUT) == 1
+
+
+def _host_loop(tmp_path):
+    so = os.path.join(str(tmp_path), "klt_host.so")
+    subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "perf", "klt_host.cpp")])
+    return C.CDLL(so)
+
+
+def test_compiled_host_loop_equals_the_referee(tmp_path):
+    """tests/perf/klt_host.cpp, the specification as compiled C++ (the yardstick of tests/perf/bench_klt.py), gives the referee's bits on
+    the edge and option cases: the specification does not depend on numpy's way of evaluating it"""
+    lib = _host_loop(tmp_path)
+    for group, cases in (("edge", kc.edge_cases()), ("option", kc.option_cases())):
+        for c, ref in zip(cases, kc.referee(group)):
+            a, n = c["args"], c["pts"].shape[0]
+            cur, back, st, why = np.zeros((n, 2)), np.zeros((n, 2)), np.zeros(n, np.uint8), np.zeros(n, np.int32)
+            nkeep, info = np.zeros(1, np.int32), np.zeros(1, np.int32)
+            first = np.array([0, n], np.int32)
+            g = None if c["guess"] is None else np.ascontiguousarray(c["guess"]).ctypes.data_as(pd)
+            lib.klt_host(C.c_int32(1), C.c_int32(c["prev"].shape[0]), C.c_int32(c["prev"].shape[1]), c["prev"].ctypes.data_as(pb), c["cur"].ctypes.data_as(pb),
+                         first.ctypes.data_as(pi), np.ascontiguousarray(c["pts"]).ctypes.data_as(pd), g, C.c_int32(a["win"]), C.c_int32(a["max_level"]),
+                         C.c_int32(a["back_level"]), C.c_int32(a["max_count"]), C.c_double(a["eps"]), C.c_double(a["min_eig"]), C.c_double(a["back_dist"]),
+                         C.c_int32(a["flags"]), cur.ctypes.data_as(pd), back.ctypes.data_as(pd), st.ctypes.data_as(pb), why.ctypes.data_as(pi),
+                         nkeep.ctypes.data_as(pi), info.ctypes.data_as(pi))
+            assert info[0] == ref["info"] and nkeep[0] == ref["n_keep"] and np.array_equal(why, ref["why"]) and np.array_equal(st, ref["status"]), c["name"]
+            assert np.array_equal(cur.view(np.uint64), ref["cur_px"].view(np.uint64)), c["name"]
+            if a["flags"] & 4:
+                assert np.array_equal(back.view(np.uint64), ref["back_px"].view(np.uint64)), c["name"]
+
+
+def compile_shim(tmp_path):
+    build.build()
+    exe = os.path.join(str(tmp_path), "shim_klt")
+    libdir = os.path.dirname(solver.LIB_PATH)
+    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_klt.cpp"),
+                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
+                           "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_klt_adapter_compiles_as_cxx14(tmp_path):
+    """TrackImageKLT binds under the reference's -std=c++14; without a GPU the shim exits non-zero with a message."""
+    exe = compile_shim(tmp_path)
+    if solver.device_count() == 0:
+        r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+        assert r.returncode != 0 and "failed" in r.stdout, r.stdout
