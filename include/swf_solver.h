@@ -71,6 +71,7 @@ enum {
  * FindReferenceSatellites and LambdaSearch's D3 loop for a batch of windows, one wavefront each), swf_batch_select_ambiguity_pairs /
  * swf_batch_ambiguity_search_selected / swf_batch_get_ambiguity_pairs (solve, tail covariance, pair selection, LAMBDA and ratio test as
  * one enqueue).  swf_batch_ambiguity_search with host pairs is unchanged.
+ * 113: no layout change; swf_batch_export_step, the debug / parity export of the last proposed step (next to swf_batch_export_vectors).
  * swf_abi_sizes reports sizeof(swf_options), sizeof(swf_summary), sizeof(swf_timing), sizeof(swf_flat_window), sizeof(swf_iteration) so a binding can check its own. */
 int swf_version(void);
 int swf_abi_sizes(int32_t out[5]);
@@ -142,12 +143,19 @@ int swf_batch_summaries(swf_batch* b, swf_summary* out);
  *       whole factor.  After an optimising solve of a system of up to 256 dimensions (240 up to library version 104) only the block the reference reads then
  *       (UpdateSchurHessianOnly, R/swf/swf_gnss.cpp:65-94) is kept: rows and columns from the 16-aligned index at or before the
  *       parameter_head tail; the rest is returned as zero (the factor lives in registers and is not written to HBM on solve
- *       paths).  SWF_EXPORT_L=1 in the environment keeps the whole factor everywhere.
+ *       paths).
  * Any pointer may be NULL.  hs_row is summary.reduced_dim. */
 int swf_batch_export_reduced(swf_batch* b, int32_t w, double* S, double* rhs, double* L);
 /* Debug/parity export of local-space vectors of window w (n_loc doubles each, ordering
  * order): gradient J^T r, squared column norms, and y = (J^T J + D)^-1 J^T r. */
 int swf_batch_export_vectors(swf_batch* b, int32_t w, double* grad, double* diag, double* y);
+/* Debug/parity export of the step of window w (n_loc doubles, ordering order, as swf_batch_export_vectors): the local-space
+ * increment of the candidate the LAST trust-region iteration proposed, x_candidate = Plus(x, step) — the dogleg step (Gauss-Newton,
+ * clipped Cauchy or interpolated) or Levenberg-Marquardt's -y, exactly as the step kernel stored it.  For a vector block x_new - x
+ * recovers it only to half an ulp of x (nothing, for an ambiguity of 1e7 cycles moved by 1e-6): this is what the entrywise step
+ * tests read.  A stream synchronisation and one copy; not on any solve path.  SWF_E_STATE unless the last solve was an optimising
+ * one (step_mode = SWF_OPTIMIZE); zero for a window whose solve proposed no step. */
+int swf_batch_export_step(swf_batch* b, int32_t w, double* step);
 int swf_batch_dims(swf_batch* b, int32_t w, int32_t* n_loc, int32_t* n_e, int32_t* n_red);
 /* Debug/parity export of the LAST linearisation of window w, factor by factor: the residual vector r [n_res] and the dense
  * Jacobian J [n_res][n_loc] (row-major; columns = local coordinates in elimination order, as swf_batch_export_vectors) exactly

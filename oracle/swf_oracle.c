@@ -1395,11 +1395,14 @@ static double now_sec(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC,
 
 /* Export buffers (analogue of ceres::internal::{lhs_out, rhs_out, lhs_out2, hs_row},
  * R/swf/swf_gnss.cpp:25-94): any of S/rhs/L may be NULL; each n_red*n_red / n_red doubles.
- * Also optional full-vector exports for tests: grad (n_loc), gn (n_loc, unscaled GN step). */
+ * Also optional full-vector exports for tests: grad (n_loc), gn (n_loc, unscaled GN step);
+ * y (n_loc): the solution of the last linear solve as it left linear_solve, (J^T J + mu D) y = J^T r, before the dogleg scaling;
+ * step (n_loc): the last proposed step in local coordinates (tests/np_step.py judges both entry by entry). */
 typedef struct oracle_export {
     double* S; double* rhs; double* L;
     double* grad; double* gn_step; double* diag;
     int32_t* loc_off;            /* [n_blocks] */
+    double* y; double* step;
 } oracle_export;
 
 int oracle_dims(const swf_flat_window* w, int32_t* n_loc, int32_t* n_e, int32_t* n_red, int32_t* n_res) {
@@ -1474,6 +1477,7 @@ int oracle_solve(const swf_flat_window* w, const swf_options* opt, swf_summary* 
     double* dsqrt = (double*)malloc(sizeof(double) * (n + 1));
     double* tmp = (double*)malloc(sizeof(double) * (n + 1));
     double* xt = (double*)malloc(sizeof(double) * (c->n_x + 1));
+    double* ysol = (double*)calloc((size_t)n + 1, sizeof(double));     /* the last linear solve's y, for the export */
     int rc = 0;
 
     /* IterationZero */
@@ -1493,6 +1497,7 @@ int oracle_solve(const swf_flat_window* w, const swf_options* opt, swf_summary* 
         /* assemble + eliminate + factor at the current point, no damping, no step */
         for (int i = 0; i < n; i++) dclamp[i] = 0.0;
         int lrc = linear_solve(c, dclamp, 0.0, c->gn);
+        memcpy(ysol, c->gn, sizeof(double) * n);
         sum->termination = lrc ? SWF_LINEAR_SOLVER_FAILURE : SWF_ASSEMBLED_ONLY;
         sum->final_cost = x_cost;
         goto done;
@@ -1538,6 +1543,7 @@ int oracle_solve(const swf_flat_window* w, const swf_options* opt, swf_summary* 
                 rec->trust_region_radius = radius;
                 continue;
             }
+            memcpy(ysol, c->gn, sizeof(double) * n);
             for (int i = 0; i < n; i++) c->step[i] = -c->gn[i];
         } else
         if (!reuse) {
@@ -1557,6 +1563,7 @@ int oracle_solve(const swf_flat_window* w, const swf_options* opt, swf_summary* 
                 if (linear_solve(c, dclamp, mu, c->gn) == 0) { lin_ok = 1; break; }
                 mu *= opt->mu_increase_factor;
             }
+            if (lin_ok) memcpy(ysol, c->gn, sizeof(double) * n);
             if (lin_ok) for (int i = 0; i < n; i++) c->gn[i] *= -dsqrt[i];     /* scaled GN step */
         }
         reuse = 1;
@@ -1659,10 +1666,12 @@ done:
         if (ex->grad) memcpy(ex->grad, c->g, sizeof(double) * n);
         if (ex->gn_step) memcpy(ex->gn_step, c->gn, sizeof(double) * n);
         if (ex->diag) memcpy(ex->diag, c->diag, sizeof(double) * n);
+        if (ex->y) memcpy(ex->y, ysol, sizeof(double) * n);
+        if (ex->step) memcpy(ex->step, c->step, sizeof(double) * n);
         if (ex->loc_off) for (int b = 0; b < c->n_blocks; b++) ex->loc_off[b] = c->loc_off[b];
     }
     ctx_store_state(c);
-    free(dclamp); free(jq); free(dsqrt); free(tmp); free(xt);
+    free(dclamp); free(jq); free(dsqrt); free(tmp); free(xt); free(ysol);
     ctx_free(c);
     sum->minimizer_time_in_seconds = now_sec() - t0;
     return rc;

@@ -30,7 +30,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 extern "C" const char* swf_last_error(void) { return g_err.c_str(); }
 void swf_internal_set_error(const std::string& m) { g_err = m; }
-extern "C" int swf_version(void) { return 112; }
+extern "C" int swf_version(void) { return 113; }
 extern "C" int swf_abi_sizes(int32_t out[5]) {
     if (!out) return fail(SWF_E_INVALID, "swf_abi_sizes: null");
     out[0] = (int32_t)sizeof(swf_options); out[1] = (int32_t)sizeof(swf_summary); out[2] = (int32_t)sizeof(swf_timing);
@@ -1729,6 +1729,17 @@ extern "C" int swf_batch_export_vectors(swf_batch* b, int32_t w, double* grad, d
     if (grad) HIPCHK(hipMemcpy(grad, b->D.g + W.loc_base, n * sizeof(double), hipMemcpyDeviceToHost));
     if (diag) HIPCHK(hipMemcpy(diag, b->D.diag + W.loc_base, n * sizeof(double), hipMemcpyDeviceToHost));
     if (y) HIPCHK(hipMemcpy(y, b->D.y + W.loc_base, n * sizeof(double), hipMemcpyDeviceToHost));
+    return SWF_OK;
+}
+
+// Debug / parity export: the step of window w's last proposed candidate (k_dogleg / k_step_eval), n_loc doubles in elimination order.
+extern "C" int swf_batch_export_step(swf_batch* b, int32_t w, double* step) {
+    DeviceGuard dg_(b ? b->device : -1);
+    if (!b || w < 0 || w >= (int)b->win.size()) return fail(SWF_E_INVALID, "bad window index");
+    if (b->last_mode != SWF_OPTIMIZE) return fail(SWF_E_STATE, "swf_batch_export_step before an optimising solve");
+    const WinRec& W = b->win[w];
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (step) HIPCHK(hipMemcpy(step, b->D.step + W.loc_base, (size_t)W.n_loc * sizeof(double), hipMemcpyDeviceToHost));
     return SWF_OK;
 }
 

@@ -1284,6 +1284,10 @@ __device__ __forceinline__ int d_dogleg(const DevBatch& B, const DevOpt& O, cons
     }
     // the step and the candidate = Plus(x, step) in one pass over the local dimensions, from the registers of the pass above; the pose
     // threads form their six step entries from the same operands (the same bits as step[]) and apply PoseLocalParameterization::Plus
+    // (Levenberg-Marquardt's step is -y itself, LevenbergMarquardtStrategy::ComputeStep: the trip through the scaled space would cost
+    // every entry the roundings of rsqrt_nr.  The step is pinned as the ROUNDED number that step[] holds before Plus adds it, so that
+    // a vector block's candidate is fl(x + step) of the stored step whatever the compiler contracts)
+    const bool lm_step = O.strategy == SWF_LEVENBERG_MARQUARDT;
     double a_s = 0, a_n = 0;
 #pragma unroll
     for (int u = 0; u < DU; u++) {
@@ -1294,7 +1298,7 @@ __device__ __forceinline__ int d_dogleg(const DevBatch& B, const DevOpt& O, cons
             // scaled step c1 g / sqrt(d) + c2 sqrt(d) y, then un-scaled (/ sqrt(d))
             double sc = c1 * (gv[u] * ir) + c2 * (dc * ir * yv[u]);
             a_s += sc * sc;
-            const double st = sc * ir;
+            const double st = pinned_d(lm_step ? -yv[u] : sc * ir);
             if (lead) step[i] = st;
             if (lxv[u] >= 0) { const double x0 = xv[u], xn = x0 + st; if (lead) B.xc[lxv[u]] = xn; if (xcl) xcl[lxv[u] - xb] = xn; const double dv = x0 - xn; a_n += dv * dv; }
         }
@@ -1305,21 +1309,28 @@ __device__ __forceinline__ int d_dogleg(const DevBatch& B, const DevOpt& O, cons
         double ir = rsqrt_nr(dc);
         double sc = c1 * (g[i] * ir) + c2 * (dc * ir * y[i]);
         a_s += sc * sc;
-        const double st = sc * ir;
+        const double st = pinned_d(lm_step ? -y[i] : sc * ir);
         if (lead) step[i] = st;
         if (a >= 0) { const double x0 = B.x[a], xn = x0 + st; if (lead) B.xc[a] = xn; if (xcl) xcl[a - xb] = xn; const double dv = x0 - xn; a_n += dv * dv; }
     }
     DST(6);
     if (p_lo >= 0) {
         double d[6], o[7];
+        if (lm_step) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) {
-            double dc = clampd(pd[k], O.min_diag, O.max_diag);
-            double ir = rsqrt_nr(dc);
-            double sc = c1 * (pg[k] * ir) + c2 * (dc * ir * py[k]);
-            d[k] = sc * ir;
+            for (int k = 0; k < 6; k++) d[k] = -py[k];
+            pose_plus(xp, d, o);
+        } else {
+            // (a branch of its own: the dogleg's Plus keeps the instructions, and so the bits, it had before the Levenberg-Marquardt form)
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                double dc = clampd(pd[k], O.min_diag, O.max_diag);
+                double ir = rsqrt_nr(dc);
+                double sc = c1 * (pg[k] * ir) + c2 * (dc * ir * py[k]);
+                d[k] = sc * ir;
+            }
+            pose_plus(xp, d, o);
         }
-        pose_plus(xp, d, o);
 #pragma unroll
         for (int k = 0; k < 7; k++) { if (lead) B.xc[p_xo + k] = o[k]; if (xcl) xcl[p_xo + k - xb] = o[k]; const double dv = xp[k] - o[k]; a_n += dv * dv; }
     }

@@ -34,7 +34,7 @@ EXPORTED = [
     "swf_version", "swf_device_count", "swf_set_device", "swf_last_error",
     "swf_batch_create", "swf_batch_destroy", "swf_batch_upload_state", "swf_batch_reset_state",
     "swf_batch_solve", "swf_batch_sync", "swf_batch_download_state", "swf_batch_summaries",
-    "swf_batch_export_reduced", "swf_batch_export_vectors", "swf_batch_dims",
+    "swf_batch_export_reduced", "swf_batch_export_vectors", "swf_batch_export_step", "swf_batch_dims",
     "swf_batch_enable_timing", "swf_batch_timing",
     "swf_problem_create", "swf_problem_destroy", "swf_add_parameter_block", "swf_has_parameter_block",
     "swf_remove_parameter_block", "swf_set_parameter_block_constant", "swf_set_parameter_block_variable",
@@ -177,6 +177,12 @@ class BatchSolver:
         _chk(lib().swf_batch_export_vectors(self._h, C.c_int32(w), g.ctypes.data_as(_pd), d.ctypes.data_as(_pd),
                                             y.ctypes.data_as(_pd)), "swf_batch_export_vectors")
         return g, d, y
+
+    def export_step(self, w=0):
+        """the step of window w's last proposed candidate, n_loc doubles in elimination order (swf_batch_export_step)"""
+        step = np.zeros(self.dims(w)["n_loc"])
+        _chk(lib().swf_batch_export_step(self._h, C.c_int32(w), step.ctypes.data_as(_pd)), "swf_batch_export_step")
+        return step
 
     def export_jacobian(self, w=0):
         """(r [n_res], J [n_res][n_loc]) of window w's last linearisation as the device holds it (swf_batch_export_jacobian)."""

@@ -18,7 +18,7 @@ _pi = C.POINTER(C.c_int32)
 
 class ExportC(C.Structure):
     _fields_ = [("S", _pd), ("rhs", _pd), ("L", _pd), ("grad", _pd), ("gn_step", _pd),
-                ("diag", _pd), ("loc_off", _pi)]
+                ("diag", _pd), ("loc_off", _pi), ("y", _pd), ("step", _pd)]
 
 
 _lib = None
@@ -115,10 +115,11 @@ def solve(win, opt=None, export=True):
     ex = ExportC()
     if export:
         out = dict(S=np.zeros((n, n)), rhs=np.zeros(n), L=np.zeros((n, n)), grad=np.zeros(nl),
-                   gn_step=np.zeros(nl), diag=np.zeros(nl), loc_off=np.zeros(win.n_blocks, np.int32))
+                   gn_step=np.zeros(nl), diag=np.zeros(nl), loc_off=np.zeros(win.n_blocks, np.int32), y=np.zeros(nl), step=np.zeros(nl))
         ex.S, ex.rhs, ex.L = _p(out["S"]), _p(out["rhs"]), _p(out["L"])
         ex.grad, ex.gn_step, ex.diag = _p(out["grad"]), _p(out["gn_step"]), _p(out["diag"])
         ex.loc_off = out["loc_off"].ctypes.data_as(_pi)
+        ex.y, ex.step = _p(out["y"]), _p(out["step"])
     sm = SummaryC()
     s = win.c_struct()
     rc = lib().oracle_solve(C.byref(s), C.byref(opt), C.byref(sm), C.byref(ex) if export else None)

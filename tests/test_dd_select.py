@@ -91,7 +91,7 @@ def test_library_exports_the_selection():
     lib = solver.lib()
     for s in NEW_SYMBOLS:
         assert s in solver.EXPORTED and hasattr(lib, s), s
-    assert lib.swf_version() == 112
+    assert lib.swf_version() == 113
     for s in ("select_ambiguity_pairs", "ambiguity_search_selected", "ambiguity_pairs"):
         assert hasattr(solver.BatchSolver, s)
     assert hasattr(solver, "dd_select_batch")

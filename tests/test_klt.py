@@ -42,7 +42,7 @@ def test_klt_symbol_exported():
     assert (solver.KLT_TRACKED, solver.KLT_FWD_LOST, solver.KLT_FWD_FLAT, solver.KLT_BACK_LOST, solver.KLT_BACK_FLAT, solver.KLT_BACK_FAR,
             solver.KLT_BORDER) == (nk.TRACKED, nk.FWD_LOST, nk.FWD_FLAT, nk.BACK_LOST, nk.BACK_FLAT, nk.BACK_FAR, nk.BORDER)
     assert (solver.KLT_WMAX, solver.KLT_LMAX, solver.KLT_NMAX) == (nk.WMAX, nk.LMAX, nk.NMAX)
-    assert lib.swf_version() == 112
+    assert lib.swf_version() == 113
     for rows, cols, lv in ((96, 128, 3), (480, 752, 3), (45, 47, 1), (24, 31, 4), (177, 201, 0)):
         assert solver.klt_pyramid_bytes(rows, cols, lv) == nk.pyramid_bytes(rows, cols, lv)
     assert solver.klt_pyramid_bytes(96, 128, 5) == 0 and solver.klt_pyramid_bytes(0, 128, 1) == 0

@@ -44,7 +44,7 @@ def test_pnp_symbol_exported():
     assert (solver.PNP_OK, solver.PNP_TOO_FEW, solver.PNP_NO_MODEL, solver.PNP_UNREFINED, solver.PNP_BAD_INPUT) == \
         (npp.OK, npp.TOO_FEW, npp.NO_MODEL, npp.UNREFINED, npp.BAD_INPUT)
     assert (solver.PNP_NMAX, solver.PNP_HMAX) == (npp.NMAX, npp.HMAX)
-    assert lib.swf_version() == 112
+    assert lib.swf_version() == 113
 
 
 def _raw_call(frames, drop=None, first=None, n=None, iterations=100, threshold=pg.THRESHOLD, flags=1):

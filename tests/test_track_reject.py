@@ -49,7 +49,7 @@ def test_track_reject_symbol_exported():
     assert "RejectWithF(" in open(os.path.join(ROOT, "include", "swf_ceres.hpp")).read()
     assert (solver.TRK_OK, solver.TRK_TOO_FEW, solver.TRK_NO_MODEL, solver.TRK_BAD_INPUT) == (npt.OK, npt.TOO_FEW, npt.NO_MODEL, npt.BAD_INPUT)
     assert (solver.TRK_NMAX, solver.TRK_HMAX) == (npt.NMAX, npt.HMAX)
-    assert lib.swf_version() == 112
+    assert lib.swf_version() == 113
 
 
 OUT_KEYS = ("status", "keep", "ni", "best", "nit", "info", "F", "uc", "up", "vel", "samples", "hyp", "count")
