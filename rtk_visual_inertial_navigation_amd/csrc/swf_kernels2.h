@@ -802,6 +802,7 @@ __global__ void __launch_bounds__(CC_NT) k_chol_col(DevBatch B, int j) {
 // =========================================================================================
 // Back-substitution of the eliminated blocks: y_e = Einv (g_e - H_ef y_f)
 // =========================================================================================
+template <bool DEFER>
 __device__ __forceinline__ void d_backsub_lm(const DevBatch& B, const DevOpt& O, int bid, double (*sc)[256]) {
     // One lane per observation (a block = up to 256 consecutive observations = whole landmarks of one window, host-built table), so every
     // lane of the Jacobian loads is live — 16 lanes per landmark left 6 of them idle at the mean track length of 10.  Two things share the
@@ -811,8 +812,16 @@ __device__ __forceinline__ void d_backsub_lm(const DevBatch& B, const DevOpt& O,
     // The per-observation terms of t are staged in LDS and one lane per landmark adds its track in observation order.
     // Loads by dependency level, each level issued as a whole (round 3 walked them one after the other — record -> window -> flags ->
     // landmark -> offsets -> values, ~8 exposed round trips of ~1.2 us on the latency path): (1) the block record; (2) every index and
-    // constant that hangs off it (clamped addresses: unconditional loads); (3) the window's flags, the state values, y and D^-2 g at
-    // the pose; (4) D^-2 g at the landmark.
+    // constant that hangs off it (clamped addresses: unconditional loads); (3) the window's flags, the landmark's offset and the 17
+    // state values proj_core takes; (4) behind proj_core, y and D^-2 g at the pose and D^-2 g at the landmark; (5) in front of the
+    // block's reduction, what only the lanes tid < nlm use behind it (lm_loc, lm_obs0, lm_g, lm_Einv of the lane's landmark: addresses
+    // from the record alone, the round trip passes behind the reduction's barriers).
+    // DEFER (the launch of its own in large batches, k_post_chol<1>): levels 4 and 5 stand where they are listed.  Without it (the one
+    // grid of the latency path: one window on an empty chip, where an exposed level is 1.2 us of the launch and registers buy
+    // nothing) level 4 is requested with level 3 and level 5 with level 2, as they were before 48 registers were counted for them
+    // across proj_core in the batch: 148 registers and 3 waves per SIMD then, 78 and 6 now.  That launch is bound by latency, not by
+    // the memory or the vector pipe, so the waves that run beside a waiting one more than pay for the extra exposed level: 61 -> 48 us
+    // per launch at 512 windows; with level 4 held across the core instead, 124 registers, 4 waves, 55 us (profiles/r12).
     const int4 rec = ((const int4*)B.lmb_rec)[bid];
     const int o0 = rec.x, cnt = rec.y, L0 = rec.z, nlm = rec.w, tid = threadIdx.x;
     const int nl = B.n_lm, n = B.n_proj;
@@ -821,36 +830,50 @@ __device__ __forceinline__ void d_backsub_lm(const DevBatch& B, const DevOpt& O,
     const int o = ho ? o0 + tid : o0, L = hl ? L0 + tid : L0;
     const int plm = B.p_lm[o], lp = B.p_lpose[o], xpo = B.p_xpose[o], xex = B.p_xex[o], xlm = B.p_xlm[o], pfr = B.p_fr[o], pll = B.p_llm[o];
     const double u0 = B.p_uv[2 * o], u1 = B.p_uv[2 * o + 1];
-    const int lloc = B.lm_loc[L], lob = B.lm_obs0[L], loe = B.lm_obs0[L + 1];
-    const double g0 = B.lm_g[0 * nl + L], g1 = B.lm_g[1 * nl + L], g2 = B.lm_g[2 * nl + L];
-    const double e00 = B.lm_Einv[0 * nl + L], e10 = B.lm_Einv[1 * nl + L], e20 = B.lm_Einv[2 * nl + L];
-    const double e11 = B.lm_Einv[3 * nl + L], e21 = B.lm_Einv[4 * nl + L], e22 = B.lm_Einv[5 * nl + L];
+    int lloc, lob, loe;
+    double g0, g1, g2, e00, e10, e20, e11, e21, e22;
+    auto level5 = [&]() {
+        lloc = B.lm_loc[L]; lob = B.lm_obs0[L]; loe = B.lm_obs0[L + 1];
+        g0 = B.lm_g[0 * nl + L]; g1 = B.lm_g[1 * nl + L]; g2 = B.lm_g[2 * nl + L];
+        e00 = B.lm_Einv[0 * nl + L]; e10 = B.lm_Einv[1 * nl + L]; e20 = B.lm_Einv[2 * nl + L];
+        e11 = B.lm_Einv[3 * nl + L]; e21 = B.lm_Einv[4 * nl + L]; e22 = B.lm_Einv[5 * nl + L];
+    };
     const WinState& s = B.ws[win];
     const WinRec& W = B.win[win];
     const int need = s.need_lin, failed = s.lin_fail;
     const int loc = B.lm_loc[plm];
-    double P[7], E[7], X[3], yp[6], vp[6];
+    double P[7], E[7], X[3];
 #pragma unroll
     for (int k = 0; k < 7; k++) { P[k] = B.x[xpo + k]; E[k] = B.x[xex + k]; }
 #pragma unroll
     for (int k = 0; k < 3; k++) X[k] = B.x[xlm + k];
+    double yp[6], vp[6], vl0 = 0, vl1 = 0, vl2 = 0;
+    auto level4 = [&]() {
 #pragma unroll
-    for (int k = 0; k < 6; k++) { const int q = lp >= 0 ? lp + k : 0; yp[k] = B.y[q]; vp[k] = B.vc[q]; }
-    double vl0 = 0, vl1 = 0, vl2 = 0;
-    { const int q = loc >= 0 ? loc : 0; vl0 = B.vc[q]; vl1 = B.vc[q + 1]; vl2 = B.vc[q + 2]; }
-    if (loc < 0) { vl0 = 0; vl1 = 0; vl2 = 0; }
+        for (int k = 0; k < 6; k++) { const int q = lp >= 0 ? lp + k : 0; yp[k] = B.y[q]; vp[k] = B.vc[q]; }
+        { const int q = loc >= 0 ? loc : 0; vl0 = B.vc[q]; vl1 = B.vc[q + 1]; vl2 = B.vc[q + 2]; }
+        if (loc < 0) { vl0 = 0; vl1 = 0; vl2 = 0; }
+    };
+    if (!DEFER) { level5(); level4(); }
     if (!need) return;                                         // uniform: the block belongs to one window
     double c0 = 0, c1 = 0, c2 = 0, aux = 0;
     if (ho) {
         // the observation's Jacobian, re-derived at the linearisation point from its inputs (pose, extrinsic and landmark sit in cache
-        // for the whole track; 16 B of image coordinates per observation) rather than read back: 144 B per observation less traffic
+        // for the whole track; 16 B of image coordinates per observation) rather than read back: 144 B per observation less traffic.
+        // kj is not zeroed in front of the core (the zeros were live across it): rows 0..11 are read only where the pose is variable,
+        // which is where the core writes them, and the landmark rows are taken as zero below where the core left them out.
         double kj[20];
-#pragma unroll
-        for (int k = 0; k < 20; k++) kj[k] = 0.0;
         proj_core<true, false>(B, o, W, P, E, X, u0, u1, lp >= 0, pll >= 0, kj);
-        double jl0 = kj[14], jl1 = kj[15], jl2 = kj[16], jl3 = kj[17], jl4 = kj[18], jl5 = kj[19];
+        if (DEFER) level4();                                     // 30 registers that are not held across the core
+        const bool hjl = pll >= 0;
+        const double jl0 = hjl ? kj[14] : 0.0, jl1 = hjl ? kj[15] : 0.0, jl2 = hjl ? kj[16] : 0.0;
+        const double jl3 = hjl ? kj[17] : 0.0, jl4 = hjl ? kj[18] : 0.0, jl5 = hjl ? kj[19] : 0.0;
+        // Sums of two products: which product the compiler contracts into the fma follows the operand order it settles for the
+        // addition, and that order follows where the loads stand.  The contractions are therefore written out, as every build up to
+        // the one that moved the loads made them: J v = jl0 vl0 + jl1 vl1 + jl2 vl2 with the first product rounded, |a|^2 with
+        // a1^2 rounded, Jl^T w with the second product rounded.  (a += b * c has one product and needs nothing.)
         double w0 = 0, w1 = 0;                                     // Jp y
-        double a0 = jl0 * vl0 + jl1 * vl1 + jl2 * vl2, a1 = jl3 * vl0 + jl4 * vl1 + jl5 * vl2;   // J v
+        double a0 = __builtin_fma(jl2, vl2, __builtin_fma(jl1, vl1, jl0 * vl0)), a1 = __builtin_fma(jl5, vl2, __builtin_fma(jl4, vl1, jl3 * vl0));   // J v
         if (lp >= 0) {
 #pragma unroll
             for (int i = 0; i < 6; i++) {
@@ -859,10 +882,11 @@ __device__ __forceinline__ void d_backsub_lm(const DevBatch& B, const DevOpt& O,
                 a0 += ja * vp[i]; a1 += jb * vp[i];
             }
         }
-        aux = a0 * a0 + a1 * a1;
-        if (pfr >= 0) { c0 = -(jl0 * w0 + jl3 * w1); c1 = -(jl1 * w0 + jl4 * w1); c2 = -(jl2 * w0 + jl5 * w1); }
+        aux = __builtin_fma(a0, a0, a1 * a1);
+        if (pfr >= 0) { c0 = -__builtin_fma(jl0, w0, jl3 * w1); c1 = -__builtin_fma(jl1, w0, jl4 * w1); c2 = -__builtin_fma(jl2, w0, jl5 * w1); }
     }
     (void)n;
+    if (DEFER) level5();                                         // 18 + 3 registers likewise
     sc[0][tid] = c0; sc[1][tid] = c1; sc[2][tid] = c2;
     {   // the block's share of |J D^-2 g|^2 (k_dogleg adds the window's blocks in order)
         __shared__ double asum[16];
@@ -945,14 +969,20 @@ __global__ void __launch_bounds__(256, (FS && !IMU) ? 5 : 1) k_eval_ps(DevBatch 
     else d_eval_imu<JAC>(B, bid - S.e[2]);
 }
 // after the reduced solve: back-substitution of the eliminated blocks, and |J D^-2 g|^2 for the Cauchy point.
-// PART 0: every segment in one grid (latency path).  Large batches launch the landmark segment (PART 1, the
-// HBM-bound one) apart from the rest (PART 2) so that it keeps its own, lower register count and full occupancy.
+// PART 0: every segment in one grid (latency path: a launch there costs its whole dependent-load chain).  Large batches launch the
+// landmark segment (PART 1, its loads deferred: d_backsub_lm<true>) apart from the rest (PART 2).  Registers no longer decide that
+// (PART 1: 78, 6 waves per SIMD; PART 2: 91, 5 waves; one grid with the deferred loads: 93, 5 waves; PART 0 as it is, with the early
+// loads: 155, 3 waves, as before); the measurement does: at 512 windows one grid with the deferred loads, landmark blocks first, bound
+// to 5 waves, takes 89.2 us against 48.0 + 38.3 = 86.2 us of the two launches (profiles/r12) — the small segments of PART 2 are rounds of blocks
+// that wait on their own load chains, and behind the landmark blocks they find the CUs no less idle than in a launch of their own.
+// PART 1 is bound to 5 waves per SIMD after the pattern of k_eval_ps, so that no later change to d_backsub_lm takes the occupancy
+// away silently (today the compiler stays below the bound by itself).
 template <int PART>
-__global__ void __launch_bounds__(256) k_post_chol(DevBatch B, DevOpt O, Segs S) {
+__global__ void __launch_bounds__(256, PART == 1 ? 5 : 1) k_post_chol(DevBatch B, DevOpt O, Segs S) {
     int bid = blockIdx.x + (PART == 2 ? S.e[0] : 0);
     __shared__ double sm_bs[PART == 2 ? 1 : 3][256];
     __shared__ double sm_pv[PART == 1 ? 1 : PRB_MAX]; __shared__ int sm_pl[PART == 1 ? 1 : PRB_MAX]; __shared__ double sm_pw[4];
-    if (PART != 2 && bid < S.e[0]) { d_backsub_lm(B, O, bid, sm_bs); return; }   // also the projection part of |J D^-2 g|^2
+    if (PART != 2 && bid < S.e[0]) { d_backsub_lm<PART == 1>(B, O, bid, sm_bs); return; }   // also the projection part of |J D^-2 g|^2
     if (PART == 1) return;
     if (bid < S.e[1]) d_backsub_clique(B, bid - S.e[0]);
     else if (bid < S.e[3]) d_jtimes_scalar<0>(B, O, bid - S.e[2]);
