@@ -12,6 +12,7 @@ Notes on two items of the plan that the code does not have as stated:
     of this referee's reach (np_linearize.py), so no case here has one."""
 import numpy as np
 
+import bitwise
 from rtk_visual_inertial_navigation_amd import synth
 from rtk_visual_inertial_navigation_amd.ordering import my_ordering
 
@@ -27,14 +28,6 @@ def _reorder(w, roles, is_const):
     w.a["order_block"], w.a["order_group"], w.n_tail = ob, og, int(nt)
     w.meta["roles"] = roles
     return w
-
-
-def with_constant(win, blocks):
-    """the same window with the given global blocks held constant, the elimination ordering re-issued"""
-    w = win.copy()
-    is_const = w.a["is_const"].copy()
-    is_const[list(blocks)] = 1
-    return _reorder(w, _roles(w), is_const)
 
 
 def _rotate(q, rotvec):
@@ -214,8 +207,8 @@ def _idepth_edges(w):
 
 
 def _stereo():
-    from test_feature_check import stereo_window
-    return stereo_window()[0]
+    import stereo_gen
+    return stereo_gen.stereo_window()[0]
 
 
 def _var_ex(head):
@@ -224,12 +217,12 @@ def _var_ex(head):
 
 def _const_landmark():
     w = synth.make_window(2, K=5, F=12, S=0, seed=42)
-    return with_constant(w, [w.bid_lm(0), w.bid_lm(5)])
+    return bitwise.with_constant(w, [w.bid_lm(0), w.bid_lm(5)], store_roles=True)
 
 
 def _imu_const():
     w = synth.make_window(3, K=5, F=10, S=5, seed=43)
-    return with_constant(w, [w.bid_pose(0), w.bid_sb(2)])
+    return bitwise.with_constant(w, [w.bid_pose(0), w.bid_sb(2)], store_roles=True)
 
 
 def _proj_depths():

@@ -10,6 +10,7 @@ EPS = 2.0 ** -52
 SHAPE_N = (3, 4, 5, 6, 8, 63, 64, 65, 200)
 ITERATIONS = (1, 63, 64, 65, 100, 128)
 COND_MAX = 1e8
+M_HYP, M_REF = 2.0, 1.0                 # measured: the docstring of test_pnp.py; test_tolerance_constants_are_the_measured_ones holds them
 ARGS = (pg.TIC, pg.RIC, pg.PBG)
 
 

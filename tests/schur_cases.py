@@ -7,12 +7,19 @@ frames) the 4-wave class, <= 36 (up to 21 frames) the 8-wave class, <= 136 (up t
 tracks of the wanted lengths (synth draws track lengths in [2, K] with mean K / 2)."""
 import numpy as np
 
+import bitwise
 from rtk_visual_inertial_navigation_amd import synth
 
-
-def _with_constant(w, pose):
-    from test_clique_mfma_gpu import _with_constant as f
-    return f(w, pose)
+# The constants of the componentwise rules, shared by test_schur_componentwise.py (which holds them to the measured ratios) and
+# test_step_componentwise.py.  name = ceil(8 x largest CPU ratio); the ratio, the route and the case it came from
+M_G = 45.0       # grad  5.60  oracle, idepth_long
+M_D = 38.0       # diag  4.67  oracle and numpy, dense_prior
+M_S = 460.0      # S     57.40 oracle, var_extrinsic (14.88 elsewhere: doppler)
+M_R = 37.0       # rhs   4.55  oracle, idepth_long
+M_L = 108.0      # L     13.47 oracle, n_red_550
+M_A = 7.0        # marginal A  0.75  numpy's S by the device's algorithm, dense_prior_tail
+M_B = 11.0       # marginal b  1.36  numpy's S by the device's algorithm, dense_prior_tail
+VACUOUS = 1e-3   # M_S 2^-52 bracket <= VACUOUS |S_ref| on every non-zero entry of S_ref
 
 
 def _idepth(w, **kw):
@@ -50,7 +57,7 @@ SCHUR = {
     # frames linked only by composite IMU-GNSS factors, landmarks on the same pose blocks
     "composite_landmarks": _composite,
     # one pose held constant: 30 x 39 and 15 x 24 cliques, projection factors with a missing block
-    "constant_pose": lambda: _with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1021), pose=2),
+    "constant_pose": lambda: bitwise.with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1021), [2]),
     # 22 observing frames (> 21): 9 row tiles = 45 tiles, the 12-consumer-wave k_lm_schur; tracks of 17 .. 22 span two 16-lane groups
     "frames_22": lambda: synth.make_window(3, K=22, F=12, S=5, seed=15),
     # tracks of 33 and 34 observations: four groups, a whole producer wave (34 frames: still the 12-consumer-wave class)

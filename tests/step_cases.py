@@ -7,6 +7,7 @@ between the two the interpolation, above the Gauss-Newton norm the Gauss-Newton 
 threshold; the test asserts 1e-6."""
 import numpy as np
 
+import bitwise
 import schur_cases as sc
 from rtk_visual_inertial_navigation_amd import synth
 from rtk_visual_inertial_navigation_amd.flat import default_options
@@ -15,22 +16,9 @@ GN, CAUCHY, INTERP = 0, 1, 2
 DOGLEG, LM = 0, 1
 
 
-def with_constant_block(win, block):
-    """the same window with one parameter block (global block id) held constant, the elimination ordering re-issued"""
-    from rtk_visual_inertial_navigation_amd.ordering import my_ordering
-    w = win.copy()
-    roles = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in w.meta["roles"].items()}
-    is_const = w.a["is_const"].copy()
-    is_const[block] = 1
-    o_b, o_g, nt = my_ordering(roles, is_const)
-    w.a["is_const"] = np.ascontiguousarray(is_const, np.uint8)
-    w.a["order_block"], w.a["order_group"], w.n_tail = o_b, o_g, int(nt)
-    return w
-
-
 def _constant_landmark():
     w = synth.make_window(3, K=6, F=30, S=5, seed=1021)
-    return with_constant_block(w, w.bid_lm(int(np.bincount(w.a["proj_idx"].reshape(-1, 3)[:, 2]).argmax())))      # the longest track's landmark
+    return bitwise.with_constant(w, [w.bid_lm(int(np.bincount(w.a["proj_idx"].reshape(-1, 3)[:, 2]).argmax()))])      # the longest track's landmark
 
 
 # windows of this file alone

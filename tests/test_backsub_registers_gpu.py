@@ -6,7 +6,7 @@ of the batch ends at the end of lm_g / lm_Einv / lm_obs0, and a closed or failed
 The landmark segment is launched by itself only from multi_processor_count windows up, so every case is a batch of
 multi_processor_count + 1 windows: tiny fillers (K = 4, F = 6, S = 2, three kinds, repeated) around the windows that carry the
 case.  Every case is batch == the same windows solved alone, bit for bit (states, iteration counts, the cost and
-step_is_successful columns of the trace), with the helpers of tests/test_gate_last_gpu.py.
+step_is_successful columns of the trace), with the helpers of tests/bitwise.py, the batches created with SWF_NO_LAT_FUSE=1.
 
 The carrying window has K = 10 frames and F = 60 landmarks of five observations each: 300 observations, two landmark blocks, the
 first nearly full (51 landmarks, 255 observations) and a short last one (9 landmarks, 45 observations).  (F = 30 gives 150
@@ -18,8 +18,7 @@ import pytest
 
 from rtk_visual_inertial_navigation_amd import synth
 from rtk_visual_inertial_navigation_amd.flat import default_options
-from test_gate_last_gpu import multi_processor_count, solve_alone, solve_batch, assert_window_equal
-from test_load_levels_gpu import with_constant_pose_and_landmark
+from bitwise import assert_window_equal, multi_processor_count, solve_alone, solve_batch, with_constant_pose_and_landmark
 
 pytestmark = pytest.mark.gpu
 
@@ -76,7 +75,7 @@ def run_case(placed, its=None):
     kinds = [placed[i] if i in placed else ("filler%d" % (i % 3), None) for i in range(n)]
     ws = [w if w is not None else filler(i % 3) for i, (_, w) in enumerate(kinds)]
     ref = [single(k, ws[i], opt, its) for i, (k, _) in enumerate(kinds)]
-    batch, sms = solve_batch(ws, opt)
+    batch, sms = solve_batch(ws, opt, no_lat_fuse=True)
     assert len(batch) == n
     return n, ref, batch, sms
 

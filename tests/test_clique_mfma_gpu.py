@@ -9,8 +9,8 @@ swf_debug_mfma_f64 on operands whose exponents spread over 2^-40 .. 2^40 and com
 exactly on the host (rational arithmetic, one rounding per fma).  Exactly one order may match, and it is the ascending one that
 k_clique_mm's slot table (CMM_SLOT_ROW in csrc/swf_clique_mm.h) assumes.
 
-The knob is read when a batch is created, so each side of a comparison is a fresh child process (this file run as a script), after
-tests/test_clique_pack_gpu.py: states, every summary field, the whole trace, and export_reduced / export_vectors of an
+The knob is read when a batch is created, so each side of a comparison is a fresh child process (tests/bitwise.py calls child() of
+this file), after tests/test_clique_pack_gpu.py: states, every summary field, the whole trace, and export_reduced / export_vectors of an
 ASSEMBLE_ELIMINATE_ONLY solve.  Both children set SWF_NO_LAT_FUSE=1, so that a handful of windows takes the batch path and class 1 exists.
 
 Shapes of the class-1 cliques in the cases (rows x columns, d_e = 9):
@@ -22,20 +22,14 @@ Shapes of the class-1 cliques in the cases (rows x columns, d_e = 9):
 class), so columns 46 and 47 of the 32 x 48 envelope are never occupied by a test: they are zero columns of the third tile either way."""
 import ctypes
 import itertools
-import os
-import subprocess
-import sys
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import bitwise
+
 KNOB = "SWF_NO_CLIQUE_MFMA"
-SUMMARY_FIELDS = ("initial_cost", "final_cost", "minimizer_time_in_seconds", "num_successful_steps", "num_unsuccessful_steps",
-                  "num_iterations", "termination", "reduced_dim", "tail_dim")
-TRACE_FIELDS = ("cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease", "trust_region_radius",
-                "model_cost_change", "step_is_successful", "step_is_valid")
 
 
 # ------------------------------------------------------------------------------------------------------------------- step 0
@@ -80,19 +74,6 @@ def test_mfma_f64_is_a_slot_ordered_fma_chain():
 
 
 # ---------------------------------------------------------------------------------------------------------------- child side
-def _with_constant(win, pose):
-    """The same window with one pose block held constant, the elimination ordering re-issued."""
-    from rtk_visual_inertial_navigation_amd.ordering import my_ordering
-    w = win.copy()
-    roles = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in w.meta["roles"].items()}
-    is_const = w.a["is_const"].copy()
-    is_const[pose] = 1
-    o_b, o_g, nt = my_ordering(roles, is_const)
-    w.a["is_const"] = np.ascontiguousarray(is_const, np.uint8)
-    w.a["order_block"], w.a["order_group"], w.n_tail = o_b, o_g, int(nt)
-    return w
-
-
 def _three(synth):
     return [synth.make_window(3, K=6, F=30, S=5, seed=1010 + i) for i in range(3)]
 
@@ -106,8 +87,8 @@ def _case(name):
     if name == "lm":
         return _three(synth), default_options(strategy=1)
     if name == "constant_pose":
-        return [synth.make_window(3, K=6, F=30, S=5, seed=1020), _with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1021), pose=2),
-                _with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1022), pose=5)], default_options()
+        return [synth.make_window(3, K=6, F=30, S=5, seed=1020), bitwise.with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1021), [2]),
+                bitwise.with_constant(synth.make_window(3, K=6, F=30, S=5, seed=1022), [5])], default_options()
     if name == "even_odd_k":
         # K = 6: the last speed-bias clique holds one IMU factor (15 rows); K = 7: every one holds two
         return [synth.make_window(3, K=6, F=30, S=5, seed=1030), synth.make_window(3, K=7, F=30, S=5, seed=1031),
@@ -127,55 +108,20 @@ def _case(name):
     raise KeyError(name)
 
 
-def _child(name, path):
-    for p in (ROOT, os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+def child(name):
     from rtk_visual_inertial_navigation_amd import solver
-    from rtk_visual_inertial_navigation_amd.flat import default_options
-    out = {}
-    # the linearisation at the uploaded state alone: the reduced system and the local vectors the eliminations wrote
-    if name != "nan_pose":
-        ws, opt = _case(name)
-        bs = solver.BatchSolver(ws)
-        bs.solve(default_options(step_mode=1), download=False)
-        for i in range(len(ws)):
-            S, rhs, _ = bs.export_reduced(i)
-            g, d, _ = bs.export_vectors(i)
-            out["w%d_elim_S" % i] = S; out["w%d_elim_rhs" % i] = rhs; out["w%d_elim_g" % i] = g; out["w%d_elim_diag" % i] = d
-        bs.close()
+    # the linearisation at the uploaded state alone (not of the NaN case), then the solve
+    out = {} if name == "nan_pose" else bitwise.dump_elimination(_case(name)[0])
     ws, opt = _case(name)
     bs = solver.BatchSolver(ws)
-    sms = bs.solve(opt)
-    for i, (w, sm) in enumerate(zip(ws, sms)):
-        for k, v in w.state().items():
-            out["w%d_state_%s" % (i, k)] = v
-        for f in SUMMARY_FIELDS:
-            out["w%d_summary_%s" % (i, f)] = np.array(getattr(sm, f))
-        rows = sm.rows()
-        for f in TRACE_FIELDS:
-            out["w%d_trace_%s" % (i, f)] = np.array([r[f] for r in rows])
+    out.update(bitwise.dump_solve(ws, bs.solve(opt)))
     bs.close()
-    np.savez(path, **out)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------- test side
 def _solve_in_child(name, path, env):
-    e = dict(os.environ)
-    for k in (KNOB, "SWF_NO_CLIQUE_PACK", "SWF_FULL_FINAL_ELIM", "SWF_NO_SPEC_EVAL"):
-        e.pop(k, None)
-    e["SWF_NO_LAT_FUSE"] = "1"
-    e.update(env)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name, path], env=e, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, "\n".join((r.stdout + r.stderr).splitlines()[-25:])
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
-
-
-def _assert_same_bytes(a, b, keys=None):
-    assert sorted(a) == sorted(b)
-    for k in sorted(a) if keys is None else keys:
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+    return bitwise.solve_in_child("test_clique_mfma_gpu", name, path, env, batch_kernels=True)
 
 
 @pytest.mark.gpu
@@ -192,19 +138,15 @@ def test_matrix_core_cliques_equal_valu_cliques_bitwise(name, tmp_path):
         # (sign, payload) an instruction hands on is not part of the contract
         keys = [k for k in sorted(mm) if not k.startswith("w1_") or k.startswith("w1_summary_")]
         assert len(keys) < len(mm)
-        _assert_same_bytes(mm, valu, keys)
+        bitwise.assert_same_bytes(mm, valu, keys)
         assert not np.all(np.isfinite(mm["w1_trace_cost"])) or term[1] != term[0], (term, mm["w1_trace_cost"])
         for i in (0, 2):
             assert all(np.all(np.isfinite(mm[k])) for k in mm if k.startswith("w%d_state_" % i) or k in ("w%d_trace_cost" % i, "w%d_trace_gradient_max_norm" % i)), i
             assert nit[i] > 1, nit
         return
-    _assert_same_bytes(mm, valu)
+    bitwise.assert_same_bytes(mm, valu)
     assert any(k.endswith("_elim_S") for k in mm)
     assert all(np.all(np.isfinite(mm[k])) for k in mm if k.endswith("_trace_gradient_max_norm") or k.endswith("_elim_S"))
     assert min(nit) > 1, nit                                                       # the solves ran: the comparison is of more than one linearisation
     if name == "early_stop":
         assert max(nit[1], nit[2], nit[3]) < min(nit[0], nit[4]), nit             # the case is a case: some windows stopped before the others
-
-
-if __name__ == "__main__":
-    _child(sys.argv[1], sys.argv[2])

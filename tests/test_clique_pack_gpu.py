@@ -1,41 +1,21 @@
 """Class-0 cliques of the batch path (receiver clocks, the dummy, small free groups) are eliminated two per wavefront by
 k_clique_pack, out of LDS sized by the batch's largest class-0 clique.  SWF_NO_CLIQUE_PACK=1 keeps the one-wavefront-per-clique
 k_clique_elim<48,32,1,0[,true]>; the two must give the same BYTES.  The knob is read when a batch is created, so each side of a
-comparison is a fresh child process (this file run as a script: it solves the named case and saves every output as an .npz):
+comparison is a fresh child process (tests/bitwise.py: it calls child() of this file on the named case and saves every output):
 states, every summary field, the whole iteration trace, and export_reduced / export_vectors of an ASSEMBLE_ELIMINATE_ONLY solve of
 the same windows.  Both children set SWF_NO_LAT_FUSE=1, so that a handful of windows takes the batch path and class 0 exists.
 
 A cfg3 window has 21 class-0 cliques (20 clocks and the dummy), so a batch of an odd number of windows has an odd total (the last
 wavefront's upper half idles) and every second window boundary falls inside a wavefront (a pair that straddles two windows)."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import bitwise
+
 KNOB = "SWF_NO_CLIQUE_PACK"
-SUMMARY_FIELDS = ("initial_cost", "final_cost", "minimizer_time_in_seconds", "num_successful_steps", "num_unsuccessful_steps",
-                  "num_iterations", "termination", "reduced_dim", "tail_dim")
-TRACE_FIELDS = ("cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease", "trust_region_radius",
-                "model_cost_change", "step_is_successful", "step_is_valid")
 
 
 # ---------------------------------------------------------------------------------------------------------------- child side
-def _with_constant(win, pose):
-    """The same window with one pose block held constant, the elimination ordering re-issued."""
-    from rtk_visual_inertial_navigation_amd.ordering import my_ordering
-    w = win.copy()
-    roles = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in w.meta["roles"].items()}
-    is_const = w.a["is_const"].copy()
-    is_const[pose] = 1
-    o_b, o_g, nt = my_ordering(roles, is_const)
-    w.a["is_const"] = np.ascontiguousarray(is_const, np.uint8)
-    w.a["order_block"], w.a["order_group"], w.n_tail = o_b, o_g, int(nt)
-    return w
-
-
 def _mixed(synth):
     """Clock cliques of 20 x 17 (cfg3 default), 10 x 12 (S = 5) and 40 x 27 (S = 20) in one batch of five windows: paired halves
     differ in n_rows and d, the LDS is sized by the largest."""
@@ -60,7 +40,7 @@ def _case(name):
                  synth.make_window(config_id=3, F=205, seed=702)], default_options(max_num_iterations=20))
     if name == "member_sets":
         base = synth.make_window(3, seed=930)
-        return [_with_constant(base, pose=2), synth.make_window(3, K=6, F=30, S=5, seed=931, doppler=True),
+        return [bitwise.with_constant(base, [2]), synth.make_window(3, K=6, F=30, S=5, seed=931, doppler=True),
                 synth.with_spp_and_fixed(synth.make_window(3, seed=932), seed=12, n_fix=2)], default_options()
     if name == "nan_pivot":
         ws = [synth.make_window(3, seed=940 + i) for i in range(3)]
@@ -69,55 +49,20 @@ def _case(name):
     raise KeyError(name)
 
 
-def _child(name, path):
-    for p in (ROOT, os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+def child(name):
     from rtk_visual_inertial_navigation_amd import solver
-    from rtk_visual_inertial_navigation_amd.flat import default_options
-    out = {}
-    # the linearisation at the uploaded state alone: the reduced system and the local vectors the eliminations wrote
-    if name != "nan_pivot":
-        ws, opt = _case(name)
-        bs = solver.BatchSolver(ws)
-        bs.solve(default_options(step_mode=1), download=False)
-        for i in range(len(ws)):
-            S, rhs, _ = bs.export_reduced(i)
-            g, d, _ = bs.export_vectors(i)
-            out["w%d_elim_S" % i] = S; out["w%d_elim_rhs" % i] = rhs; out["w%d_elim_g" % i] = g; out["w%d_elim_diag" % i] = d
-        bs.close()
+    # the linearisation at the uploaded state alone (not of the NaN case), then the solve
+    out = {} if name == "nan_pivot" else bitwise.dump_elimination(_case(name)[0])
     ws, opt = _case(name)
     bs = solver.BatchSolver(ws)
-    sms = bs.solve(opt)
-    for i, (w, sm) in enumerate(zip(ws, sms)):
-        for k, v in w.state().items():
-            out["w%d_state_%s" % (i, k)] = v
-        for f in SUMMARY_FIELDS:
-            out["w%d_summary_%s" % (i, f)] = np.array(getattr(sm, f))
-        rows = sm.rows()
-        for f in TRACE_FIELDS:
-            out["w%d_trace_%s" % (i, f)] = np.array([r[f] for r in rows])
+    out.update(bitwise.dump_solve(ws, bs.solve(opt)))
     bs.close()
-    np.savez(path, **out)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------- test side
 def _solve_in_child(name, path, env):
-    e = dict(os.environ)
-    for k in (KNOB, "SWF_FULL_FINAL_ELIM", "SWF_NO_SPEC_EVAL"):
-        e.pop(k, None)
-    e["SWF_NO_LAT_FUSE"] = "1"
-    e.update(env)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name, path], env=e, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, "\n".join((r.stdout + r.stderr).splitlines()[-25:])
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
-
-
-def _assert_same_bytes(a, b):
-    assert sorted(a) == sorted(b)
-    for k in sorted(a):
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+    return bitwise.solve_in_child("test_clique_pack_gpu", name, path, env, batch_kernels=True)
 
 
 @pytest.mark.gpu
@@ -126,7 +71,7 @@ def test_two_cliques_per_wavefront_equal_one_per_wavefront_bitwise(name, tmp_pat
     both = {"SWF_FULL_FINAL_ELIM": "1"} if name == "mixed_full_final" else {}
     pack = _solve_in_child(name, str(tmp_path / "pack.npz"), dict(both))
     one = _solve_in_child(name, str(tmp_path / "one.npz"), dict(both, **{KNOB: "1"}))
-    _assert_same_bytes(pack, one)
+    bitwise.assert_same_bytes(pack, one)
     n_win = len([k for k in pack if k.endswith("_summary_num_iterations")])
     nit = [int(pack["w%d_summary_num_iterations" % i]) for i in range(n_win)]
     term = [int(pack["w%d_summary_termination" % i]) for i in range(n_win)]
@@ -143,7 +88,3 @@ def test_two_cliques_per_wavefront_equal_one_per_wavefront_bitwise(name, tmp_pat
     else:
         assert any(k.endswith("_elim_S") for k in pack)
         assert all(np.all(np.isfinite(pack[k])) for k in pack if k.endswith("_trace_gradient_max_norm") or k.endswith("_elim_S"))
-
-
-if __name__ == "__main__":
-    _child(sys.argv[1], sys.argv[2])

@@ -3,7 +3,6 @@ swf_batch_select_ambiguity_pairs / _ambiguity_search_selected / _get_ambiguity_p
 against the plain-Python referee (tests/np_ddselect.py).  The operator has no product and every sum runs in a fixed order, so
 every comparison is for equality: pairs, counts, refs and role as integers, cost as bits."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -12,10 +11,10 @@ import pytest
 import ddselect_gen as dg
 import fixprior_gen as fg
 import np_ddselect as nd
+from shim import compile_shim
 from rtk_visual_inertial_navigation_amd import build, solver, synth
 from rtk_visual_inertial_navigation_amd.flat import default_options
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["swf_dd_select_batch", "swf_batch_select_ambiguity_pairs", "swf_batch_ambiguity_search_selected",
                "swf_batch_get_ambiguity_pairs"]
 
@@ -124,20 +123,10 @@ def test_host_rejections_need_no_device():
         assert np.all(a == 77)
 
 
-def _compile_shim(tmp_path):
-    build.build()
-    exe = os.path.join(str(tmp_path), "shim_dd_select")
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_dd_select.cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_adapter_compiles_as_cxx14_and_fails_without_gpu(tmp_path):
     """LambdaSearch's reference election and D3 loop bind to swf_ceres::SelectDoubleDifferences (include/swf_ceres.hpp) under the
     reference's -std=c++14; without a GPU the call reports failure."""
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_dd_select")
     if solver.device_count() > 0:
         pytest.skip("a GPU is present (the run is covered by the gpu test)")
     r = subprocess.run([exe], capture_output=True, text=True)
@@ -284,7 +273,7 @@ def test_dd_select_batch_device_resident_matches_host_path():
 
 @pytest.mark.gpu
 def test_adapter_runs_on_gpu(tmp_path):
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_dd_select")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     y = [3.02, -7.05, 11.00, 0.96, 5.51, -2.47, 8.49, 4.03]

@@ -10,21 +10,21 @@ referee on the inputs below, solved by the CPU oracle: largest ratio of a deviat
 landmark 3e5 m behind the camera); times the margin of 8 for the device's fused multiply-adds, rounded up: M_TOL = 18.
 Largest device deviation on MI355X, in units of the bracket: not measured; every GPU test prints it (`deviation / bracket`)."""
 import functools
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import bitwise
 import idepth_gen
 import np_features as nf
 import oracle_binding as ob
+from shim import compile_shim
+from stereo_gen import stereo_window
 from rtk_visual_inertial_navigation_amd import build, solver, synth
 from rtk_visual_inertial_navigation_amd.flat import FlatWindow, default_options
-from rtk_visual_inertial_navigation_amd.ordering import my_ordering
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -52
 M_TOL = 18.0
 SINGLE = [(2, 11, 8), (2, 13, 8), (3, 21, 24), (3, 22, 24)]          # (config, seed, injected landmarks)
@@ -85,82 +85,6 @@ def bitwise_equal(a, b):
                for k in ("mean_err", "depth", "n_obs", "flags", "rejected")) and a["n_feat"] == b["n_feat"]
 
 
-def with_constant_landmarks(win, landmarks):
-    w = win.copy()
-    is_const = w.a["is_const"].copy()
-    for l in landmarks:
-        is_const[w.bid_lm(l)] = 1
-    ob_, og_, nt = my_ordering(w.meta["roles"], is_const)
-    w.a["is_const"] = np.ascontiguousarray(is_const, np.uint8)
-    w.a["order_block"], w.a["order_group"], w.n_tail = ob_, og_, int(nt)
-    return w
-
-
-def _project(pose, ex, X, pbg):
-    R, Re = synth.q_to_R(pose[3:]), synth.q_to_R(ex[3:])
-    pc = Re.T @ (R.T @ (X - pose[:3]) + pbg - ex[:3])
-    return pc[:2] / pc[2]
-
-
-def stereo_window(seed=31):
-    """A hand-built window: a small synthetic window whose short tracks are inverse depths (kind 0), with a second camera's
-    extrinsic appended to the pose pool (variable, so the factors that name it take the generic path), stereo world-point factors
-    for three landmarks, kind-1 and kind-2 inverse-depth factors, one inverse depth that only a kind-2 factor names (constant),
-    and one landmark without any factor (constant).  Meant to be checked at the uploaded state."""
-    base = idepth_gen.convert_short_tracks(synth.make_window(3, K=6, F=30, S=5, seed=seed), max_track=3)
-    a = base.a
-    rng = np.random.default_rng(seed)
-    nP, nS, nL, nC = base.n_pose, base.n_sb, base.n_lm, base.n_sc
-    K = base.meta["K"]                                   # the first camera's extrinsic is pose K
-    pose = a["pose"].reshape(-1, 7)
-    ex2 = pose[K].copy(); ex2[:3] += synth.q_to_R(ex2[3:]) @ np.array([0.11, 0.0, 0.0])
-    pose2 = np.vstack([pose, ex2]); e2 = nP
-    sh = lambda b: int(b) if b < nP else int(b) + 1      # global block ids behind the pose pool move up by one
-    pidx = a["proj_idx"].reshape(-1, 3).copy(); puv = a["proj_uv"].reshape(-1, 2).copy()
-    lm = a["lm"].reshape(-1, 3)
-    # an unobserved landmark: landmark 0 loses its factors and is held constant
-    keep = pidx[:, 2] != 0
-    pidx, puv = pidx[keep], puv[keep]
-    add_i, add_uv = [], []
-    for l in (1, 2, 3):
-        for p, e, _ in pidx[pidx[:, 2] == l]:
-            add_i.append([p, e2, l]); add_uv.append(_project(pose2[p], ex2, lm[l], base.pbg) + rng.normal(0, 1e-3, 2))
-    pidx = np.vstack([pidx, np.array(add_i, np.int32)]); puv = np.vstack([puv, np.array(add_uv)])
-    kind = list(a["idp_kind"]); iidx = [list(r) for r in a["idp_idx"].reshape(-1, 5)]; ipts = [r.copy() for r in a["idp_pts"].reshape(-1, 6)]
-    sc = list(a["sc"])
-    lams = sorted(set(r[4] for r in iidx))
-    for c in lams[:4]:
-        first = next(i for i, r in enumerate(iidx) if r[4] == c)
-        fi, fj, ex = iidx[first][0], iidx[first][1], iidx[first][2]
-        pts_i = ipts[first][:3]
-        Xa = synth.q_to_R(pose2[ex][3:]) @ (pts_i / sc[c]) + pose2[ex][:3] - base.pbg
-        Xw = synth.q_to_R(pose2[fi][3:]) @ Xa + pose2[fi][:3]
-        uvr_j = _project(pose2[fj], ex2, Xw, base.pbg) + rng.normal(0, 1e-3, 2)
-        uvr_i = _project(pose2[fi], ex2, Xw, base.pbg) + rng.normal(0, 1e-3, 2)
-        kind.append(1); iidx.append([fi, fj, ex, e2, c]); ipts.append(np.concatenate([pts_i, uvr_j, [1.0]]))
-        kind.append(2); iidx.append([-1, -1, ex, e2, c]); ipts.append(np.concatenate([pts_i, uvr_i, [1.0]]))
-    lone = len(sc); sc.append(0.2)                       # an inverse depth only a kind-2 factor names: 5 m along pts_i
-    pts_l = np.array([0.05, -0.02, 1.0])
-    Xb = synth.q_to_R(pose2[K][3:]) @ (pts_l / 0.2) + pose2[K][:3] - base.pbg
-    kind.append(2); iidx.append([-1, -1, K, e2, lone])
-    ipts.append(np.concatenate([pts_l, _project(np.array([0, 0, 0, 0, 0, 0, 1.0]), ex2, Xb, base.pbg) + 2e-3, [1.0]]))
-    is_const = np.concatenate([a["is_const"][:nP], [0], a["is_const"][nP:], [1]]).astype(np.uint8)
-    is_const[nP + 1 + nS + 0] = 1
-    roles = {}
-    for k, v in base.meta["roles"].items():
-        roles[k] = [sh(b) for b in v] if isinstance(v, (list, tuple, np.ndarray)) else (sh(v) if v is not None else None)
-    roles["extrinsics"] = list(roles["extrinsics"]) + [e2]
-    o_b, o_g, nt = my_ordering(roles, is_const)
-    kw = {k: v for k, v in a.items() if k not in ("pose", "sc", "is_const", "order_block", "order_group", "proj_idx", "proj_uv",
-                                                   "idp_kind", "idp_idx", "idp_pts", "prior_blk")}
-    w = FlatWindow(pose=pose2, sc=np.array(sc), is_const=is_const, order_block=o_b, order_group=o_g, n_tail=int(nt),
-                   proj_idx=pidx, proj_uv=puv, idp_kind=np.array(kind, np.int32), idp_idx=np.array(iidx, np.int32), idp_pts=np.array(ipts),
-                   prior_blk=np.array([sh(b) for b in a["prior_blk"]], np.int32), proj_sqrt_info=base.proj_sqrt_info,
-                   proj_loss_a=base.proj_loss_a, pbg=base.pbg, gw=base.gw, base=base.base, meta=dict(base.meta, roles=roles), **kw)
-    assert w.n_blocks == is_const.size
-    return w, lone
-
-
 # ---------------------------------------------------------------------------------------------------------------- CPU tier
 def test_feature_symbols_exported():
     import ctypes
@@ -218,20 +142,10 @@ def test_referee_refuses_disagreeing_anchors():
         nf.table(w)
 
 
-def _compile_shim(tmp_path):
-    build.build()
-    exe = os.path.join(str(tmp_path), "shim_outliers")
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_outliers.cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_outliers_adapter_compiles_as_cxx14(tmp_path):
     """ImagePostprocess's call binds to swf_ceres::OutliersRejection under the reference's -std=c++14; without a GPU the shim
     exits non-zero with a message."""
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_outliers")
     if solver.device_count() == 0:
         r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
         assert r.returncode != 0 and "failed" in r.stdout, r.stdout
@@ -334,7 +248,7 @@ def test_generic_path_and_constant_landmarks():
     """Factors with a variable extrinsic (GF_PROJX on the generic path) and constant landmarks are covered like any other."""
     w = single_window(3, 21, 24)
     wx = synth.with_variable_extrinsic(w)
-    wc = with_constant_landmarks(w, [0, 3, 7, 11])
+    wc = bitwise.with_constant(w, [w.bid_lm(l) for l in (0, 3, 7, 11)])
     bs, res = solve_and_check([wx, wc])
     assert_matches_referee(wx, res[0], label="variable extrinsic")
     assert_matches_referee(wc, res[1], label="constant landmarks")
@@ -459,7 +373,7 @@ def test_problem_api_by_key():
 
 @pytest.mark.gpu
 def test_outliers_adapter_run_matches_referee(tmp_path):
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_outliers")
     out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
     print(out.stdout)
     assert out.returncode == 0, out.stdout

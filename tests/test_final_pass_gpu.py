@@ -1,47 +1,23 @@
 """The solve's final linearisation forms the gradient alone (k_finalize reads nothing else of it): the clique kernels stop behind
 g / diag / vc / graw / dgraw, the landmark pass skips the 3x3 inverse and its records.  SWF_FULL_FINAL_ELIM=1 restores the complete
-elimination in that pass.  The knob is read when a batch is created, so each side of a comparison is a fresh child process (this
-file run as a script: it solves the named case and saves every output as an .npz); the two files must hold the same bytes:
+elimination in that pass.  The knob is read when a batch is created, so each side of a comparison is a fresh child process
+(tests/bitwise.py: it calls child() of this file on the named case and saves every output); the two files must hold the same bytes:
 states, every summary field, the whole iteration trace (gradient_max_norm of every iteration included), and what tail_covariance /
 ambiguity_search / check_features return behind the solve — no consumer reads what the final pass no longer writes.
 
 The second group is about the |J D^-2 g|^2 pass of k_post_chol (g_aux): model_cost_change and the trust-region radius of every
 iteration are the same bits in the speculative flow and in the two-pass flow (SWF_NO_SPEC_EVAL=1), and for a window alone and
 inside a batch."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import bitwise
+
 KNOB = "SWF_FULL_FINAL_ELIM"
-SUMMARY_FIELDS = ("initial_cost", "final_cost", "minimizer_time_in_seconds", "num_successful_steps", "num_unsuccessful_steps",
-                  "num_iterations", "termination", "reduced_dim", "tail_dim")
-TRACE_FIELDS = ("cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease", "trust_region_radius",
-                "model_cost_change", "step_is_successful", "step_is_valid")
 S_AMB = 9
 
 
 # ---------------------------------------------------------------------------------------------------------------- child side
-def _with_constant(win, pose=None, landmark=None):
-    """The same window with one pose block and / or one landmark block held constant, the elimination ordering re-issued."""
-    from rtk_visual_inertial_navigation_amd.ordering import my_ordering
-    w = win.copy()
-    K = w.meta["K"]
-    roles = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in w.meta["roles"].items()}
-    is_const = w.a["is_const"].copy()
-    if pose is not None:
-        is_const[pose] = 1
-    if landmark is not None:
-        is_const[(K + 1) + K + landmark] = 1
-    o_b, o_g, nt = my_ordering(roles, is_const)
-    w.a["is_const"] = np.ascontiguousarray(is_const, np.uint8)
-    w.a["order_block"], w.a["order_group"], w.n_tail = o_b, o_g, int(nt)
-    return w
-
-
 def _case(name):
     """-> (windows, options, consumers?)"""
     from rtk_visual_inertial_navigation_amd import synth
@@ -60,7 +36,7 @@ def _case(name):
         return [cg.make_window(rng, 5, 2, 8, F=30)], default_options(), False
     if name == "constant_blocks":
         base = synth.make_window(3, seed=830)
-        return [_with_constant(base, pose=2), _with_constant(base, landmark=3), base], default_options(), False
+        return [bitwise.with_constant(base, [2]), bitwise.with_constant(base, [base.bid_lm(3)]), base], default_options(), False
     if name == "early_stop":
         still = synth.make_window(2, seed=706, perturb=False)
         return ([synth.make_window(config_id=3, F=103, seed=701), still, synth.make_window(3, seed=707), still.copy(),
@@ -76,23 +52,11 @@ def _case(name):
     raise KeyError(name)
 
 
-def _child(name, path):
-    for p in (ROOT, os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+def child(name):
     from rtk_visual_inertial_navigation_amd import solver
     ws, opt, consumers = _case(name)
     bs = solver.BatchSolver(ws)
-    sms = bs.solve(opt)
-    out = {}
-    for i, (w, sm) in enumerate(zip(ws, sms)):
-        for k, v in w.state().items():
-            out["w%d_state_%s" % (i, k)] = v
-        for f in SUMMARY_FIELDS:
-            out["w%d_summary_%s" % (i, f)] = np.array(getattr(sm, f))
-        rows = sm.rows()
-        for f in TRACE_FIELDS:
-            out["w%d_trace_%s" % (i, f)] = np.array([r[f] for r in rows])
+    out = bitwise.dump_solve(ws, bs.solve(opt))
     if consumers:
         tc = bs.tail_covariance()
         am = bs.ambiguity_search([[(j, 0) for j in range(1, S_AMB)]] * len(ws))
@@ -106,25 +70,13 @@ def _child(name, path):
             for k in ("mean_err", "depth", "n_obs", "flags", "rejected"):
                 out["w%d_feat_%s" % (i, k)] = fc[i][k]
     bs.close()
-    np.savez(path, **out)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------- test side
 def _solve_in_child(name, path, env):
-    e = dict(os.environ)
-    for k in (KNOB, "SWF_NO_SPEC_EVAL"):
-        e.pop(k, None)
-    e.update(env)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name, path], env=e, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, "\n".join((r.stdout + r.stderr).splitlines()[-25:])
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
-
-
-def _assert_same_bytes(a, b, keys=None):
-    assert sorted(a) == sorted(b)
-    for k in (keys if keys is not None else sorted(a)):
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
+    """The children run without SWF_NO_LAT_FUSE: a case takes the launch path its own batch size gives it."""
+    return bitwise.solve_in_child("test_final_pass_gpu", name, path, env, batch_kernels=False)
 
 
 @pytest.mark.gpu
@@ -132,7 +84,7 @@ def _assert_same_bytes(a, b, keys=None):
 def test_gradient_only_final_pass_equals_full_elimination_bitwise(name, tmp_path):
     grad = _solve_in_child(name, str(tmp_path / "grad.npz"), {})
     full = _solve_in_child(name, str(tmp_path / "full.npz"), {KNOB: "1"})
-    _assert_same_bytes(grad, full)
+    bitwise.assert_same_bytes(grad, full, nan_equal=False)                 # the same bytes, and no NaN anywhere
     nit = [int(grad[k]) for k in sorted(grad) if k.endswith("_summary_num_iterations")]
     print(name, "iterations per window:", nit)
     assert all(np.all(np.isfinite(grad[k])) for k in grad if k.endswith("_trace_gradient_max_norm"))
@@ -149,14 +101,10 @@ def test_cauchy_pass_outputs_equal_two_pass_flow_and_single_window_bitwise(tmp_p
     spec = _solve_in_child("aux_batch", str(tmp_path / "spec.npz"), {})
     two = _solve_in_child("aux_batch", str(tmp_path / "two.npz"), {"SWF_NO_SPEC_EVAL": "1"})
     assert len(aux(spec)) == 6
-    _assert_same_bytes(spec, two)
+    bitwise.assert_same_bytes(spec, two, nan_equal=False)
     for i in range(3):
         one = _solve_in_child("aux_single%d" % i, str(tmp_path / ("one%d.npz" % i)), {})
         for k in sorted(one):
             kb = "w%d_" % i + k[len("w0_"):]
             assert np.array_equal(one[k], spec[kb]), (i, k)
         assert np.any(one["w0_trace_model_cost_change"] != 0.0)
-
-
-if __name__ == "__main__":
-    _child(sys.argv[1], sys.argv[2])

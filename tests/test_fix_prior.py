@@ -15,10 +15,10 @@ import pytest
 import fixprior_cases as fc
 import fixprior_gen as fg
 import np_fixprior as nf
+from shim import compile_shim
 from rtk_visual_inertial_navigation_amd import build, solver
 from rtk_visual_inertial_navigation_amd.flat import default_options
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # derived on the CPU (see the module docstring and DESIGN.md 3k): largest float64-referee deviation 0.046 / 0.399 / 0.341 / 0.007 / 0.186
 M = dict(A=1, b=4, JtJ=3, Jtr=1, eig=2)
 NEW_SYMBOLS = ["swf_prior_fix_batch", "swf_batch_fix_prior", "swf_batch_get_fixed_prior", "swf_batch_install_fixed_prior",
@@ -99,19 +99,9 @@ def test_argument_errors_are_reported_before_any_device_is_touched():
     assert solver.lib().swf_batch_install_fixed_prior(None) == -2
 
 
-def _compile_shim(tmp_path):
-    build.build()
-    exe = os.path.join(str(tmp_path), "shim_fix_prior")
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_fix_prior.cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_fix_and_hold_adapter_compiles_as_cxx14(tmp_path):
     """swf_ceres::FixAndHoldPrior under the reference's -std=c++14; without a device it reports failure, with one it succeeds."""
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_fix_prior")
     r = subprocess.run([exe], capture_output=True, text=True)
     if solver.device_count() > 0:
         assert r.returncode == 0, r.stdout + r.stderr
@@ -448,7 +438,7 @@ def test_problem_path_and_cxx_adapter_against_the_batch_path(tmp_path, saz):
     prob.AddLinearPrior(kept, out["J"], out["r0"], out["x0"])
     prob.close()
     # the C++14 adapter on the same inputs: the same device code, the same numbers
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_fix_prior")
     dim = 15 + S
     cur = np.concatenate([win.a["pose"].reshape(-1, 7)[0], win.a["sb"].reshape(-1, 9)[0], [float(blocks[int(b)][0]) for b in win.a["prior_blk"][2:]]])
     path = os.path.join(str(tmp_path), "in.txt")

@@ -6,91 +6,24 @@ same rule touches in k_assemble_flat, k_chol_rr4, k_clique_pack and the clique s
 measured, not kept: profiles/r11/README.md).
 
 Every case is batch == the same windows solved alone, bit for bit (states, iteration counts, the cost and step_is_successful
-columns of the trace), after tests/test_load_levels_gpu.py; the batches are created with SWF_NO_LAT_FUSE=1, so that three to five
+columns of the trace), with the helpers of tests/bitwise.py; the batches are created with SWF_NO_LAT_FUSE=1 (no_lat_fuse=True), so that three to five
 small windows take the batch kernels; the single windows run without it (the latency path: other launches, the same sums) except
 under Levenberg-Marquardt (see that case).  The reduced system of an ASSEMBLE_ELIMINATE_ONLY solve of the batch is compared with
 the CPU oracle at the tolerances of tests/test_gpu_parity.py (S, g, diag 1e-11; rhs 1e-10)."""
-import ctypes
-import ctypes.util
-import os
-from contextlib import contextmanager, nullcontext
-
 import numpy as np
 import pytest
 
 import oracle_binding as ob
+from bitwise import (ELIMINATE_ONLY, assert_batch_equals_singles, assert_window_equal, batch_kernels, multi_processor_count, rel, solve_alone,
+                     solve_batch, with_constant_pose_and_landmark)
 from rtk_visual_inertial_navigation_amd import synth, solver
 from rtk_visual_inertial_navigation_amd.flat import default_options
-from test_load_levels_gpu import with_constant_pose_and_landmark, rel, KEYS, ELIMINATE_ONLY
 
 pytestmark = pytest.mark.gpu
 
 
-@contextmanager
-def batch_kernels():
-    """SWF_NO_LAT_FUSE=1 while a batch is created and solved (the knob is read when the plan is built)."""
-    old = os.environ.get("SWF_NO_LAT_FUSE")
-    os.environ["SWF_NO_LAT_FUSE"] = "1"
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ["SWF_NO_LAT_FUSE"]
-        else:
-            os.environ["SWF_NO_LAT_FUSE"] = old
-
-
-def multi_processor_count():
-    """hipDeviceGetAttribute(hipDeviceAttributeMultiprocessorCount) of the current device, from the HIP runtime the library links."""
-    solver.lib()
-    hip = ctypes.CDLL(ctypes.util.find_library("amdhip64") or "libamdhip64.so")
-    n, dev = ctypes.c_int(0), ctypes.c_int(0)
-    assert hip.hipGetDevice(ctypes.byref(dev)) == 0
-    assert hip.hipDeviceGetAttribute(ctypes.byref(n), 63, dev) == 0          # 63: hipDeviceAttributeMultiprocessorCount
-    assert 1 <= n.value <= 1024, n.value
-    return n.value
-
-
 def small(K, seed, **kw):
     return synth.make_window(3, K=K, F=30, S=5, seed=seed, **kw)
-
-
-def solve_alone(w, opt, batch_shapes=False):
-    """One window by itself: on the latency path (other launches, the same sums under dogleg), or, batch_shapes, through the batch
-    kernels like the batch it is compared with."""
-    c = w.copy()
-    with (batch_kernels() if batch_shapes else nullcontext()):
-        bs = solver.BatchSolver([c])
-        sm = bs.solve(opt)[0]
-    out = (c, sm.num_iterations, [r["cost"] for r in sm.rows()], [r["step_is_successful"] for r in sm.rows()], sm.termination)
-    bs.close()
-    return out
-
-
-def solve_batch(ws, opt):
-    batch = [w.copy() for w in ws]
-    with batch_kernels():
-        bs = solver.BatchSolver(batch)
-        sms = bs.solve(opt)
-        bs.close()
-    return batch, sms
-
-
-def assert_window_equal(i, single, wb, sm):
-    c, nit, costs, ok, _ = single
-    assert sm.num_iterations == nit, i
-    assert [r["cost"] for r in sm.rows()] == costs, i
-    assert [r["step_is_successful"] for r in sm.rows()] == ok, i
-    for k in KEYS:
-        assert np.array_equal(c.a[k], wb.a[k]), (i, k)
-
-
-def assert_batch_equals_singles(ws, opt, batch_shapes=False):
-    singles = [solve_alone(w, opt, batch_shapes) for w in ws]
-    batch, sms = solve_batch(ws, opt)
-    for i, (single, wb, sm) in enumerate(zip(singles, batch, sms)):
-        assert_window_equal(i, single, wb, sm)
-    return singles, sms
 
 
 def assert_reduced_system_matches_oracle(ws):
@@ -112,7 +45,7 @@ def test_unfilled_last_blocks_and_odd_clique_count_equal_single_bitwise():
     """K = 5, 6 and 7 frames: 4 + 5 + 6 = 15 IMU factors do not fill the last block of 8, the class-0 cliques of the three windows
     are an odd number (the last pair's upper half sits out), and K = 6 ends on a speed-bias clique of a single IMU factor."""
     ws = [small(5, 1101), small(6, 1102), small(7, 1103)]
-    _, sms = assert_batch_equals_singles(ws, default_options())
+    _, sms = assert_batch_equals_singles(ws, default_options(), no_lat_fuse=True)
     assert min(sm.num_iterations for sm in sms) > 1
     assert_reduced_system_matches_oracle(ws)
 
@@ -123,7 +56,7 @@ def test_finished_windows_at_both_ends_of_the_batch_equal_single_bitwise():
     blocks run, and their records are the first and the last of every table."""
     still = synth.make_window(2, seed=706, perturb=False)
     ws = [still, synth.make_window(config_id=3, F=103, seed=701), small(5, 1111), still.copy()]
-    _, sms = assert_batch_equals_singles(ws, default_options(max_num_iterations=20))
+    _, sms = assert_batch_equals_singles(ws, default_options(max_num_iterations=20), no_lat_fuse=True)
     its = [sm.num_iterations for sm in sms]
     print("iterations per window:", its)
     assert its[0] == its[3] and its[0] < max(its[1], its[2]), its      # the case is a case: both ends stopped while the middle ran
@@ -135,7 +68,7 @@ def test_constant_pose_and_landmark_equal_single_bitwise():
     wc = with_constant_pose_and_landmark(small(6, 1121))
     assert wc.a["is_const"][2] == 1
     ws = [small(7, 1122), small(5, 1123), wc]
-    assert_batch_equals_singles(ws, default_options())
+    assert_batch_equals_singles(ws, default_options(), no_lat_fuse=True)
     assert_reduced_system_matches_oracle(ws)
 
 
@@ -144,7 +77,7 @@ def test_nan_pose_between_healthy_windows_leaves_the_neighbours_alone():
     ws[1].a["pose"].reshape(-1, 7)[1, 0] = np.nan
     opt = default_options()
     singles = [solve_alone(w, opt) for w in ws]
-    batch, sms = solve_batch(ws, opt)
+    batch, sms = solve_batch(ws, opt, no_lat_fuse=True)
     for i in (0, 2):
         assert_window_equal(i, singles[i], batch[i], sms[i])
         assert sms[i].num_iterations > 1 and np.all(np.isfinite(batch[i].a["pose"]))
@@ -158,7 +91,7 @@ def test_levenberg_marquardt_equal_single_bitwise():
     of this case, cost of iteration 7, 24.96931854727333 against 24.96931854727422), so the windows alone take the batch kernels
     too: one window per launch against three."""
     ws = [small(5, 1141), with_constant_pose_and_landmark(small(6, 1142)), small(7, 1143)]
-    _, sms = assert_batch_equals_singles(ws, default_options(strategy=1), batch_shapes=True)
+    _, sms = assert_batch_equals_singles(ws, default_options(strategy=1), no_lat_fuse=True, batch_shapes=True)
     assert min(sm.num_iterations for sm in sms) > 1
 
 
@@ -169,7 +102,7 @@ def test_more_windows_than_compute_units_equal_single_bitwise():
     kinds = [synth.make_window(3, K=4, F=6, S=2, seed=1151 + i) for i in range(3)]
     opt = default_options()
     singles = [solve_alone(w, opt) for w in kinds]
-    batch, sms = solve_batch([kinds[i % 3] for i in range(n)], opt)
+    batch, sms = solve_batch([kinds[i % 3] for i in range(n)], opt, no_lat_fuse=True)
     assert len(batch) == n
     for i in range(n):
         assert_window_equal(i, singles[i % 3], batch[i], sms[i])

@@ -24,6 +24,7 @@ import pytest
 import gnss_epoch_gen as gg
 import np_factors as npf
 import np_gnss_epoch as nge
+from shim import compile_shim
 from rtk_visual_inertial_navigation_amd import build, solver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -247,20 +248,10 @@ def test_gnss_epoch_symbols_exported():
     assert (solver.GES_CONVERGED, solver.GES_MAX_ITER, solver.GES_RANK_DEFICIENT) == (nge.CONVERGED, nge.MAX_ITER, nge.RANK_DEFICIENT)
 
 
-def _compile_shim(tmp_path):
-    build.build()
-    exe = os.path.join(str(tmp_path), "shim_gnss_epoch")
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_gnss_epoch.cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_gnss_epoch_adapter_compiles_as_cxx14(tmp_path):
     """The seed solve and the first fix bind to swf_ceres::GnssEpochSolve under the reference's -std=c++14; without a GPU the shim exits
     non-zero with a message."""
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_gnss_epoch")
     if solver.device_count() == 0:
         r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
         assert r.returncode != 0 and "failed" in r.stdout, r.stdout
@@ -634,7 +625,7 @@ def _parse_run(out, tag):
 
 @pytest.mark.gpu
 def test_gnss_epoch_adapter_run_matches_referee(tmp_path):
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_gnss_epoch")
     out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
     print(out.stdout)
     assert out.returncode == 0, out.stdout

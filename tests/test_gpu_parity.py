@@ -1138,9 +1138,9 @@ def test_batched_triangulation_matches_oracle():
     """SURVEY 8f rank 4: FeatureManager::triangulate (two-view branch) for a batch of features, one lane each, against the
     oracle: same one-sided Jacobi, same formulas -> agreement at rounding level scaled by the depth; the degenerate and
     out-of-range cases take the same branches."""
-    from test_oracle import _triangulation_scene
+    from oracle_scenes import triangulation_scene
     rng = np.random.default_rng(9)
-    Ps, Rs, tic, ric, pbg, start, pt0, pt1, Xw = _triangulation_scene(rng, n_frames=40, n_feat=5000, pbg=np.array([0.1, -0.3, 0.2]))
+    Ps, Rs, tic, ric, pbg, start, pt0, pt1, Xw = triangulation_scene(rng, n_frames=40, n_feat=5000, pbg=np.array([0.1, -0.3, 0.2]))
     pt0 += rng.normal(0, 1e-3, pt0.shape); pt1 += rng.normal(0, 1e-3, pt1.shape)
     # a few degenerate rows: identical observations in both frames (zero parallax), behind-the-camera, out-of-range frames
     pt1[:5] = pt0[:5]; pt0[5:10] = -3 * pt0[5:10] + 1.0; pt1[5:10] = -2.0
@@ -1466,14 +1466,14 @@ def test_windows_with_composite_factors_match_oracle_solver():
 def test_inverse_depth_projection_factors_match_oracle():
     """Row a2: the three inverse-depth projection factors evaluated for a batch on the device against the oracle's restatement
     (same formulas: agreement at rounding level), all kinds mixed in one launch; blocks a kind does not have come back zero."""
-    from test_oracle import _idepth_scene
+    from oracle_scenes import idepth_scene
     rng = np.random.default_rng(52)
     pbg = synth.PBG; si = synth.FOCAL_LENGTH / synth.FEATUREWEIGHTINVERSE
     n = 600
     poses, lam, kind, idx, pts, ref = [], [], [], [], [], []
     for q in range(n):
         k = q % 3
-        Pi, Pj, ex, ex2, pts_i, inv_dep = _idepth_scene(rng)
+        Pi, Pj, ex, ex2, pts_i, inv_dep = idepth_scene(rng)
         pj = nf.proj_idepth_residual(k, Pi, Pj, ex, ex2, inv_dep, pts_i, np.zeros(3), si, pbg) / si + rng.normal(0, 1e-3, 2)
         pts_j = np.array([pj[0], pj[1], 1.0])
         b = len(poses)

@@ -11,6 +11,7 @@ from rtk_visual_inertial_navigation_amd.flat import default_options
 
 from rtk_visual_inertial_navigation_amd import synth, solver, build
 from rtk_visual_inertial_navigation_amd.ordering import my_ordering
+from shim import compile_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -88,23 +89,12 @@ def test_no_cpu_fallback_without_gpu():
         solver.BatchSolver([w])
 
 
-def _compile_shim_example(tmp_path, name="shim_example"):
-    import subprocess
-    build.build()
-    exe = os.path.join(str(tmp_path), name)
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", name + ".cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_ceres_shaped_cpp_header_compiles_and_fails_loudly_without_gpu(tmp_path):
     """Estimator code in the reference's style (ceres::Problem / AddResidualBlock / ceres::Solve)
     compiles against include/swf_ceres.hpp; without a GPU the solve reports final_cost > 1e10
     (the failure convention the reference checks, R/swf/swf_image.cpp:220-223)."""
     import subprocess
-    exe = _compile_shim_example(tmp_path)
+    exe = compile_shim(tmp_path, "shim_example")
     if solver.device_count() > 0:
         pytest.skip("a GPU is present (the run is covered by the gpu test)")
     r = subprocess.run([exe], capture_output=True, text=True)
@@ -116,7 +106,7 @@ def test_reference_constructor_signatures_of_the_adapter(tmp_path):
     (R/factor/marginalization_factor.h:106): the adapter takes the reference's own objects (stand-ins with its member names and Eigen's
     accessors here) and files their contents in the C-ABI's record layouts — the prior's columns re-ordered to the order of its blocks."""
     import subprocess
-    exe = _compile_shim_example(tmp_path, "shim_reference_ctors")
+    exe = compile_shim(tmp_path, "shim_reference_ctors")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "reference constructors: ok" in r.stdout, r.stdout + r.stderr
 
@@ -125,7 +115,7 @@ def test_globalmarge_sequence_compiles_against_the_adapter(tmp_path):
     """SWFOptimization::GlobalMarge (R/swf/swf_image.cpp:343-433) statement by statement — GetParameterBlocks, GetResidualBlocks,
     ->is_use, GetResidualBlocksForParameterBlock, GetParameterBlocksForResidualBlock, parameter_head, is_optimize — compiles
     against include/swf_ceres.hpp (it runs on the GPU tier)."""
-    _compile_shim_example(tmp_path, "shim_globalmarge")
+    compile_shim(tmp_path, "shim_globalmarge")
 
 
 def test_reference_constructor_solve_compiles_as_cxx14(tmp_path):
@@ -134,7 +124,7 @@ def test_reference_constructor_solve_compiles_as_cxx14(tmp_path):
     UpdateSchur reads them (R/swf/swf_gnss.cpp:25-94) — compiles with the reference's -std=c++14 (CMakeLists.txt:5); without a GPU
     the solve reports the failure convention."""
     import subprocess
-    exe = _compile_shim_example(tmp_path, "shim_reference_solve")
+    exe = compile_shim(tmp_path, "shim_reference_solve")
     if solver.device_count() == 0:
         r = subprocess.run([exe], capture_output=True, text=True)
         assert r.returncode == 1 and "Final cost: 1.000000e+300" in r.stdout
@@ -146,7 +136,7 @@ def test_solve_built_through_the_reference_constructors_runs_on_gpu(tmp_path):
     the reference's member names; every hidden GNSS epoch in its own allocation) solves to the same bits, the hidden epochs are
     written back into their own memory, and UpdateSchur's / UpdateSchurHessianOnly's reads of the raw globals see the reduced system."""
     import subprocess
-    exe = _compile_shim_example(tmp_path, "shim_reference_solve")
+    exe = compile_shim(tmp_path, "shim_reference_solve")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "bit for bit" in r.stdout and "reference solve: ok" in r.stdout
@@ -155,7 +145,7 @@ def test_solve_built_through_the_reference_constructors_runs_on_gpu(tmp_path):
 @pytest.mark.gpu
 def test_globalmarge_sequence_runs_on_gpu(tmp_path):
     import subprocess
-    exe = _compile_shim_example(tmp_path, "shim_globalmarge")
+    exe = compile_shim(tmp_path, "shim_globalmarge")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "GlobalMarge: 4 kept blocks, prior n = 24" in r.stdout and "position error after the slide" in r.stdout
@@ -164,7 +154,7 @@ def test_globalmarge_sequence_runs_on_gpu(tmp_path):
 @pytest.mark.gpu
 def test_ceres_shaped_cpp_example_runs_on_gpu(tmp_path):
     import subprocess
-    exe = _compile_shim_example(tmp_path)
+    exe = compile_shim(tmp_path, "shim_example")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "Iterations:" in r.stdout
@@ -174,7 +164,7 @@ def test_multi_gpu_example_compiles_and_the_c_defaults_match_the_python_ones(tmp
     """The in-process multi-device entry (swf_batch_create_sharded + swf_solve_batches) compiles from plain C++ against
     include/swf_solver.h; swf_default_options fills the struct flat.default_options() fills.  Without a GPU the example reports it."""
     import subprocess
-    exe = _compile_shim_example(tmp_path, "shim_multi_gpu")
+    exe = compile_shim(tmp_path, "shim_multi_gpu")
     from rtk_visual_inertial_navigation_amd.flat import OptionsC, default_options
     o = OptionsC()
     solver.lib().swf_default_options.restype = None
@@ -193,7 +183,7 @@ def test_multi_gpu_example_compiles_and_the_c_defaults_match_the_python_ones(tmp
 @pytest.mark.gpu
 def test_multi_gpu_example_runs_on_gpu(tmp_path):
     import subprocess
-    exe = _compile_shim_example(tmp_path, "shim_multi_gpu")
+    exe = compile_shim(tmp_path, "shim_multi_gpu")
     for mask in ("0", "1"):
         r = subprocess.run([exe, mask], capture_output=True, text=True)
         assert r.returncode == 0, r.stdout + r.stderr

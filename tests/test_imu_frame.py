@@ -23,6 +23,7 @@ import pytest
 
 import np_imu_frame as nif
 import imu_frame_gen as ig
+from shim import compile_shim
 from rtk_visual_inertial_navigation_amd import build, solver, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -280,20 +281,10 @@ def test_host_side_validation_needs_no_device():
                                            bias.ctypes.data_as(pd), nz, out.ctypes.data_as(pd), C.c_int32(0), None) == E_INVALID
 
 
-def _compile_shim(tmp_path):
-    build.build()
-    exe = os.path.join(str(tmp_path), "shim_imu_frame")
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_imu_frame.cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_imu_frame_adapter_compiles_as_cxx14(tmp_path):
     """ImuIntegrate binds to swf_ceres::ImuIntegrate under the reference's -std=c++14; without a GPU the shim exits non-zero with a
     message."""
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_imu_frame")
     if solver.device_count() == 0:
         r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
         assert r.returncode != 0 and "failed" in r.stdout, r.stdout
@@ -498,7 +489,7 @@ def test_window_fed_by_the_frame_front_evaluates_as_with_the_referee():
 
 @pytest.mark.gpu
 def test_imu_frame_adapter_runs(tmp_path):
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_imu_frame")
     out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
     print(out.stdout)
     assert out.returncode == 0 and "imu frame ok" in out.stdout, out.stdout

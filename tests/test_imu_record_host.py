@@ -6,9 +6,9 @@ device): the records validate for batches of mixed shapes on a full-size and a t
 damaged record is reported."""
 import pytest
 
+from bitwise import with_constant_pose_and_landmark
+from plan_cases import clique_batches, plan_check
 from rtk_visual_inertial_navigation_amd import synth
-from test_plan_host import plan_check
-from test_clique_pack_host import _batches
 
 E_INVALID = -2
 IMU_REC = 8                       # corrupt_table id of imu_rec (swf_debug_plan_check)
@@ -16,7 +16,7 @@ IMU_REC = 8                       # corrupt_table id of imu_rec (swf_debug_plan_
 
 @pytest.mark.parametrize("name", ["mixed", "envelope", "beyond", "one", "free"])
 def test_imu_records_validate(name):
-    wins = _batches()[name]
+    wins = clique_batches()[name]
     for n_cu in (256, 8):
         for flags in (0, 1):
             rc, msg, _ = plan_check(wins, n_cu, flags=flags)
@@ -24,7 +24,7 @@ def test_imu_records_validate(name):
 
 
 def test_a_damaged_imu_record_is_reported():
-    wins = _batches()["mixed"]
+    wins = clique_batches()["mixed"]
     n_imu = sum(int(w.a["imu_idx"].size) // 4 for w in wins)
     assert n_imu >= 10
     for flags in (0, 1):
@@ -36,7 +36,6 @@ def test_a_damaged_imu_record_is_reported():
     rc, msg, _ = plan_check(wins, corrupt=(IMU_REC, n_imu))
     assert rc == E_INVALID and "nothing to corrupt" in msg, msg
     # a window with a constant pose (Jacobian offsets of -1 in its records) validates
-    from test_load_levels_gpu import with_constant_pose_and_landmark
     wc = with_constant_pose_and_landmark(synth.make_window(3, K=6, F=30, S=5, seed=931))
     for flags in (0, 1):
         rc, msg, _ = plan_check([wins[1], wc], flags=flags)

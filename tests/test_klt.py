@@ -14,6 +14,7 @@ import pytest
 import klt_cases as kc
 import klt_gen as kg
 import np_klt as nk
+from shim import compile_shim
 from rtk_visual_inertial_navigation_amd import build, solver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -265,19 +266,9 @@ def test_compiled_host_loop_equals_the_referee(tmp_path):
                 assert np.array_equal(back.view(np.uint64), ref["back_px"].view(np.uint64)), c["name"]
 
 
-def compile_shim(tmp_path):
-    build.build()
-    exe = os.path.join(str(tmp_path), "shim_klt")
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_klt.cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_klt_adapter_compiles_as_cxx14(tmp_path):
     """TrackImageKLT binds under the reference's -std=c++14; without a GPU the shim exits non-zero with a message."""
-    exe = compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_klt")
     if solver.device_count() == 0:
         r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
         assert r.returncode != 0 and "failed" in r.stdout, r.stdout

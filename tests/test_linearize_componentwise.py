@@ -33,6 +33,7 @@ import pytest
 
 import linearize_cases as lc
 import np_linearize as nl
+from plan_cases import plan_check
 from rtk_visual_inertial_navigation_amd.flat import default_options
 
 EPS = nl.EPS
@@ -157,7 +158,6 @@ PRIOR_CHUNKS = {"prior_65": 1, "prior_97": 4, "prior_130": 5, "prior_516": 17}
 @pytest.mark.parametrize("name", list(lc.CASES))
 def test_case_reaches_its_branch(name):
     """what the window or the plan shows of the branch the case exists for; the plan accepts the window; no elevation near a float32 tie"""
-    from test_plan_host import plan_check
     w = lc.window(name)
     f = lc.facts(w)
     assert name not in REACHES or REACHES[name](f), (name, f)

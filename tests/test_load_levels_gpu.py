@@ -3,93 +3,21 @@ record, then every index of the lane's observation with the observation clamped 
 then applies the block's gate), and a batch whose cliques of every one-wavefront size class feed the assembly.
 
 Every case is batch == the same windows solved alone, bit for bit, plus the reduced system against the CPU oracle at the
-tolerances of tests/test_gpu_parity.py (S, g, diag 1e-11, rhs 1e-10)."""
-import numpy as np
+tolerances of tests/test_gpu_parity.py (S, g, diag 1e-11, rhs 1e-10), with the helpers of tests/bitwise.py; the batches are created
+with the environment as it stands (no_lat_fuse=False), not under SWF_NO_LAT_FUSE=1."""
 import pytest
 
-import oracle_binding as ob
-from rtk_visual_inertial_navigation_amd import synth, solver
+from bitwise import assert_batch_equals_singles, assert_reduced_system_matches_oracle_and_single, with_constant_pose_and_landmark
+from rtk_visual_inertial_navigation_amd import synth
 from rtk_visual_inertial_navigation_amd.flat import default_options
-from rtk_visual_inertial_navigation_amd.ordering import my_ordering
 
 pytestmark = pytest.mark.gpu
 
 FS_BLK = 256                      # observations per frame-sum block (csrc/swf_kernels.h)
-KEYS = ("pose", "sb", "lm", "sc")
-ELIMINATE_ONLY = 1                # step_mode SWF_ASSEMBLE_ELIMINATE_ONLY: linearise, eliminate, assemble, factor — no step
-
-
-def rel(a, b):
-    a = np.asarray(a); b = np.asarray(b)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-300))
 
 
 def n_obs(w):
     return int(w.a["proj_idx"].shape[0])
-
-
-def with_constant_pose_and_landmark(win, pose=2, landmark=3):
-    """The same window with one pose block and one landmark block held constant (their observations then carry no pose / no
-    landmark Jacobian), and the elimination ordering re-issued for the new set of variable blocks."""
-    w = win.copy()
-    K = w.meta["K"]
-    roles = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in w.meta["roles"].items()}
-    is_const = w.a["is_const"].copy()
-    is_const[pose] = 1
-    is_const[(K + 1) + K + landmark] = 1
-    o_b, o_g, nt = my_ordering(roles, is_const)
-    w.a["is_const"] = np.ascontiguousarray(is_const, np.uint8)
-    w.a["order_block"], w.a["order_group"], w.n_tail = o_b, o_g, int(nt)
-    return w
-
-
-def solve_alone(w, opt):
-    c = w.copy()
-    bs = solver.BatchSolver([c])
-    sm = bs.solve(opt)[0]
-    out = (c, sm.num_iterations, [r["cost"] for r in sm.rows()], [r["step_is_successful"] for r in sm.rows()])
-    bs.close()
-    return out
-
-
-def assert_batch_equals_singles(ws, opt):
-    singles = [solve_alone(w, opt) for w in ws]
-    batch = [w.copy() for w in ws]
-    bs = solver.BatchSolver(batch)
-    sms = bs.solve(opt)
-    for i, ((c, nit, costs, ok), wb, sm) in enumerate(zip(singles, batch, sms)):
-        assert sm.num_iterations == nit, i
-        assert [r["cost"] for r in sm.rows()] == costs, i
-        assert [r["step_is_successful"] for r in sm.rows()] == ok, i
-        for k in KEYS:
-            assert np.array_equal(c.a[k], wb.a[k]), (i, k)
-    bs.close()
-    return singles, sms
-
-
-def assert_reduced_system_matches_oracle_and_single(ws):
-    """ELIMINATE_ONLY through the batch: every window's exported reduced system equals, bit for bit, what the window alone
-    exports, and matches the oracle's."""
-    opt = default_options(step_mode=ELIMINATE_ONLY)
-    alone = []
-    for w in ws:
-        bs = solver.BatchSolver([w.copy()])
-        bs.solve(opt)
-        alone.append((bs.export_reduced(0), bs.export_vectors(0)))
-        bs.close()
-    bs = solver.BatchSolver([w.copy() for w in ws])
-    bs.solve(opt)
-    for i, w in enumerate(ws):
-        S, rhs, L = bs.export_reduced(i)
-        g, dg, y = bs.export_vectors(i)
-        (S1, rhs1, L1), (g1, dg1, y1) = alone[i]
-        assert np.array_equal(S, S1) and np.array_equal(rhs, rhs1) and np.array_equal(L, L1), i
-        assert np.array_equal(g, g1) and np.array_equal(dg, dg1) and np.array_equal(y, y1), i
-        _, eo = ob.solve(w.copy(), opt)
-        assert rel(S, eo["S"]) < 1e-11 and np.abs(S - S.T).max() == 0, i
-        assert rel(rhs, eo["rhs"]) < 1e-10, i
-        assert rel(g, eo["grad"]) < 1e-11 and rel(dg, eo["diag"]) < 1e-11, i
-    bs.close()
 
 
 def short_block_windows():
@@ -103,7 +31,7 @@ def short_block_windows():
 def test_short_last_frame_sum_block_batch_equals_single_bitwise():
     w6, w2 = short_block_windows()
     ws = [w6, synth.make_window(3, K=6, F=30, S=5, seed=703), w2]
-    assert_batch_equals_singles(ws, default_options())
+    assert_batch_equals_singles(ws, default_options(), no_lat_fuse=False)
     assert_reduced_system_matches_oracle_and_single(ws)
 
 
@@ -114,7 +42,7 @@ def test_constant_pose_and_landmark_last_in_batch_equals_single_bitwise():
     wc = with_constant_pose_and_landmark(w6)
     assert wc.a["is_const"][2] == 1 and n_obs(wc) % FS_BLK == 6
     ws = [synth.make_window(3, K=6, F=30, S=5, seed=704), synth.make_window(3, seed=705), wc]
-    assert_batch_equals_singles(ws, default_options())
+    assert_batch_equals_singles(ws, default_options(), no_lat_fuse=False)
     assert_reduced_system_matches_oracle_and_single(ws)
 
 
@@ -127,7 +55,7 @@ def test_stopped_windows_next_to_iterating_ones_equal_single_bitwise():
     still = synth.make_window(2, seed=706, perturb=False)
     ws = [w6, still, synth.make_window(3, seed=707), still.copy(), w2]
     opt = default_options(max_num_iterations=20)
-    singles, sms = assert_batch_equals_singles(ws, opt)
+    singles, sms = assert_batch_equals_singles(ws, opt, no_lat_fuse=False)
     its = [sm.num_iterations for sm in sms]
     print("iterations per window:", its)
     assert max(its[1], its[2], its[3]) < min(its[0], its[4]) and its[3] == its[1], its      # the case is a case: they stopped before the others
@@ -138,7 +66,7 @@ def test_levenberg_marquardt_cost_only_path_equals_single_bitwise():
     w6, w2 = short_block_windows()
     ws = [w6, with_constant_pose_and_landmark(w2), synth.make_window(3, K=6, F=30, S=5, seed=708)]
     for jac in (0, 1):
-        assert_batch_equals_singles(ws, default_options(strategy=1, jacobi_scaling=jac))
+        assert_batch_equals_singles(ws, default_options(strategy=1, jacobi_scaling=jac), no_lat_fuse=False)
 
 
 def test_cliques_of_every_size_class_reduced_system_equals_single_bitwise():
@@ -150,4 +78,4 @@ def test_cliques_of_every_size_class_reduced_system_equals_single_bitwise():
     wb = synth.with_spp_and_fixed(synth.make_window(3, seed=710), seed=12, n_fix=2)
     ws = [wa, synth.make_window(3, K=6, F=30, S=5, seed=711, doppler=True), wb, with_constant_pose_and_landmark(wa)]
     assert_reduced_system_matches_oracle_and_single(ws)
-    assert_batch_equals_singles(ws, default_options())
+    assert_batch_equals_singles(ws, default_options(), no_lat_fuse=False)

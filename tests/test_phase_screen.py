@@ -23,6 +23,7 @@ import pytest
 
 import np_phase as nph
 import phase_gen as pg
+from shim import compile_shim
 from rtk_visual_inertial_navigation_amd import build, solver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -258,20 +259,10 @@ def test_referee_partner_propagation_and_reset_all():
     assert q["flags"].tolist() == [0, nph.SLIP_CODE | nph.NEW_AMB]
 
 
-def _compile_shim(tmp_path):
-    build.build()
-    exe = os.path.join(str(tmp_path), "shim_phase_screen")
-    libdir = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_phase_screen.cpp"),
-                           "-o", exe, "-L" + libdir, "-lswf_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_phase_screen_adapter_compiles_as_cxx14(tmp_path):
     """GnssPreprocess's screen binds to swf_ceres::PhaseScreen under the reference's -std=c++14; without a GPU the shim exits non-zero
     with a message."""
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_phase_screen")
     if solver.device_count() == 0:
         r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
         assert r.returncode != 0 and "failed" in r.stdout, r.stdout
@@ -513,7 +504,7 @@ def test_device_memory_bad_epoch_reports_minus_one():
 
 @pytest.mark.gpu
 def test_phase_screen_adapter_run_matches_referee(tmp_path):
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_phase_screen")
     out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
     print(out.stdout)
     assert out.returncode == 0, out.stdout

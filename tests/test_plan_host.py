@@ -2,7 +2,6 @@
 every kind the GPU tier solves must validate at a full-size and at a tiny chip, the rejections keep their codes and messages, a
 damaged table is reported (the validator's negative control), and a stand-alone program runs the same code under the address and
 undefined-behaviour sanitizers."""
-import ctypes
 import glob
 import os
 import subprocess
@@ -13,26 +12,11 @@ import pytest
 import cfg5_marg_gen
 import composite_gen
 import rtk_topology_gen as rt
-from rtk_visual_inertial_navigation_amd import build, solver, synth
-from rtk_visual_inertial_navigation_amd.flat import FlatWindowC
+from plan_cases import plan_check
+from rtk_visual_inertial_navigation_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_UNSUPPORTED = -2, -3
-INFO = ("ls_var", "ls_qpb", "ls_gqpb", "ls_folded", "lat_fuse", "want_aux", "want_Linv", "want_Wk", "asm_programs", "n_pch_split", "max_red", "n_pch")
-
-
-def plan_check(wins, n_cu=256, ls_variant=0, ls_qpb=0, ls_grad_qpb=0, flags=0, corrupt=(0, 0)):
-    """(return code, swf_last_error, info) of swf_debug_plan_check on the windows."""
-    build.build()
-    lib = ctypes.CDLL(solver.LIB_PATH)
-    lib.swf_last_error.restype = ctypes.c_char_p
-    cs = [w.c_struct() for w in wins]
-    arr = (ctypes.POINTER(FlatWindowC) * len(cs))(*[ctypes.pointer(c) for c in cs])
-    info = (ctypes.c_int32 * len(INFO))()
-    rc = lib.swf_debug_plan_check(arr, ctypes.c_int32(len(cs)), ctypes.c_int32(n_cu), ctypes.c_int32(ls_variant), ctypes.c_int32(ls_qpb),
-                                  ctypes.c_int32(ls_grad_qpb), ctypes.c_int32(flags), ctypes.c_int32(corrupt[0]), ctypes.c_int32(corrupt[1]), info)
-    return rc, (lib.swf_last_error() or b"").decode(), dict(zip(INFO, info))
-
 
 def _golden():
     from golden.make_golden import load_case

@@ -23,8 +23,9 @@ import pytest
 import np_pnp as npp
 import pnp_cases as pc
 import pnp_gen as pg
+from pnp_cases import M_HYP, M_REF
+from shim import compile_shim
 from rtk_visual_inertial_navigation_amd import solver
-from test_pnp import M_HYP, M_REF, _compile_shim
 
 SENTINEL = -7.0
 MARGIN = 1e-9
@@ -330,7 +331,7 @@ def test_chained_with_triangulation_on_device_memory():
 
 @pytest.mark.gpu
 def test_pnp_adapter_runs(tmp_path):
-    exe = _compile_shim(tmp_path)
+    exe = compile_shim(tmp_path, "shim_pnp")
     out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
     print(out.stdout)
     assert out.returncode == 0 and "pnp ok" in out.stdout, out.stdout

@@ -28,19 +28,11 @@ import np_dense as nd
 import np_schur as ns
 import oracle_binding as ob
 import schur_cases as sc
+from schur_cases import M_A, M_B, M_D, M_G, M_L, M_R, M_S, VACUOUS
 from rtk_visual_inertial_navigation_amd.flat import default_options
 
 EPS = ns.EPS
-# name = ceil(8 x largest CPU ratio); the ratio, the route and the case it came from
-M_G = 45.0       # grad  5.60  oracle, idepth_long
-M_D = 38.0       # diag  4.67  oracle and numpy, dense_prior
-M_S = 460.0      # S     57.40 oracle, var_extrinsic (14.88 elsewhere: doppler)
-M_R = 37.0       # rhs   4.55  oracle, idepth_long
-M_L = 108.0      # L     13.47 oracle, n_red_550
-M_A = 7.0        # marginal A  0.75  numpy's S by the device's algorithm, dense_prior_tail
-M_B = 11.0       # marginal b  1.36  numpy's S by the device's algorithm, dense_prior_tail
 M = dict(g=M_G, diag=M_D, S=M_S, rhs=M_R, L=M_L, A=M_A, b=M_B)
-VACUOUS = 1e-3   # M_S 2^-52 bracket <= VACUOUS |S_ref| on every non-zero entry of S_ref
 OLD_RULE = 1e-11
 
 needs_longdouble = pytest.mark.skipif(np.finfo(np.longdouble).eps >= np.finfo(np.float64).eps,

@@ -42,7 +42,9 @@ import np_schur as ns
 import np_step as st
 import oracle_binding as ob
 import step_cases as sp
-from test_schur_componentwise import M_G, M_L, M_R, M_S, VACUOUS
+from bitwise import multi_processor_count
+from plan_cases import plan_check
+from schur_cases import M_G, M_L, M_R, M_S, VACUOUS
 from rtk_visual_inertial_navigation_amd.flat import default_options
 
 EPS = ns.EPS
@@ -367,7 +369,6 @@ def test_case_reaches_its_branch():
     assert nd.local_layout(sp.window("n_loc_over_1024"))[1] > 1024 and nd.local_layout(sp.window("n_loc_over_4096"))[1] > 4096
     # launch shapes, from the host-only plan (swf_debug_plan_check): one window takes the latency path (k_post_chol<0>, the fused step or
     # k_dogleg<16, 4>), SWF_NO_LAT_FUSE (flag 1) and the batches the batch path (k_dogleg<4, 2>); 256 = the MI355X's CU count
-    from test_plan_host import plan_check
     for wins, flags, lat in (([sp.window("ragged")], 0, 1), ([sp.window("ragged")], 1, 0), (_batch(sp.BATCH_N)[0], 0, 0), (_batch(260)[0], 0, 0),
                              ([sp.window("n_loc_over_1024")], 1, 0), ([sp.window("n_loc_over_4096")], 0, 1), ([sp.window("n_loc_over_4096")], 1, 0)):
         rc, msg, info = plan_check(wins, 256, flags=flags)
@@ -507,19 +508,6 @@ def test_device_knobs_componentwise_and_bit_identical(env, monkeypatch):
         same_bits(B, ref[n][2])
 
 
-def cu_count():
-    """the device's CU count: from torch where torch sees the device, else from the HIP runtime the library links (torch reports no HIP
-    device in some test processes; test_gate_last_gpu.multi_processor_count reads hipDeviceAttributeMultiprocessorCount)"""
-    try:
-        import torch
-        if torch.cuda.is_available():
-            return int(torch.cuda.get_device_properties(0).multi_processor_count)
-    except Exception:
-        pass
-    from test_gate_last_gpu import multi_processor_count
-    return multi_processor_count()
-
-
 def _batch(n):
     ws = [sp.window(k) for k in sp.BATCH_HEAD]
     return [ws[i % len(ws)] for i in range(n)], [sp.BATCH_HEAD[i % len(ws)] for i in range(n)]
@@ -541,7 +529,7 @@ def test_device_batch_33_componentwise_and_bit_identical():
 @needs_longdouble
 def test_device_batch_beyond_the_cu_count_componentwise_and_bit_identical():
     """(CU count + 4) windows: k_post_chol<1> and <2> run only when n_win >= n_cu.  Eight sampled windows plus the first and the last."""
-    n = cu_count() + 4
+    n = multi_processor_count() + 4
     ws, names = _batch(n)
     runs = device_runs(ws, sp.options())
     alone = {k: device_runs([sp.window(k)], sp.options())[0] for k in sp.BATCH_HEAD}

@@ -11,6 +11,7 @@ SHAPE_N = (7, 8, 9, 63, 64, 65, 200, 1024)
 ITERATIONS = (1, 255, 256, 257, 1000)
 LONG_ITERATIONS = 1000                  # judged by the scan replay and the masks only
 KAPPA_MAX = 1e10
+M_HYP, M_LIFT = 43.0, 3.0               # measured: the docstring of test_track_reject.py; test_tolerance_constants_are_the_measured_ones holds them
 MOVING = ("general", "forward", "sideways")
 E2E_SEED = 20000
 TRUTH_ITERATIONS = 1000                 # OpenCV's default: at 40 % outliers one sample in 60 is clean
