@@ -30,6 +30,7 @@
 //   initFramePoseByPnP() + solvePoseByPnP()     R/feature/feature_manager.cpp:164-243 -> swf_pnp_frame_batch (InitFramePoseByPnP below)
 //   rejectWithF() + undistortedPts() + ptsVelocity()  R/feature/feature_tracker.cpp:265-294, :334-376 -> swf_track_reject_batch (RejectWithF below)
 //   trackImage(): calcOpticalFlowPyrLK forward + reverse, the 0.5 px gate, inBorder   R/feature/feature_tracker.cpp:98-141 -> swf_klt_track_batch (TrackImageKLT below)
+//   trackImage(): setMask() + cv::goodFeaturesToTrack + addPoints()   R/feature/feature_tracker.cpp:148-165, :44-79 -> swf_gftt_detect_batch (DetectFeatures below)
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
@@ -983,8 +984,8 @@ inline bool RejectWithF(const Pts& cur_pts, const Pts& prev_pts, const double ca
 //   flow_back                  FLOW_BACK: the reverse pass from the previous positions with 1 level and the 0.5 px gate
 // Returns true when the call succeeded and the pair is SWF_KLT_OK: cur_pts holds the tracked positions, out->status is what the
 // reference's status is after the reverse check and inBorder, for ReduceVector below; out->why says which test dropped a point.
-// A non-finite position (SWF_KLT_BAD_INPUT) returns false with an empty status.  goodFeaturesToTrack, setMask, the id / track_cnt
-// bookkeeping, setPrediction itself and the stereo branch stay with the caller.
+// A non-finite position (SWF_KLT_BAD_INPUT) returns false with an empty status.  The n++ of track_cnt, setPrediction itself and the
+// stereo branch stay with the caller; setMask, goodFeaturesToTrack and addPoints are DetectFeatures below.
 struct TrackImageKLTResult {
     int info = -1, n_keep = 0, levels = 0;              // levels: max_level of the forward pass that gave the result (1 or 3)
     std::vector<uint8_t> status;
@@ -1030,6 +1031,63 @@ inline bool TrackImageKLT(const uint8_t* prev_img, const uint8_t* cur_img, int r
         for (int32_t i = 0; i < n; i++) { (*cur_pts)[(size_t)i].x = (float)out->cur_px[(size_t)i * 2]; (*cur_pts)[(size_t)i].y = (float)out->cur_px[(size_t)i * 2 + 1]; }
     }
     return ok;
+}
+
+// Where the points to track come from: setMask(), cv::goodFeaturesToTrack(cur_img, n_pts, MAX_CNT - cur_pts.size(), 0.01, MIN_DIST, mask)
+// and addPoints() of FeatureTracker::trackImage (R/feature/feature_tracker.cpp:148-165) for one tracker state on the device
+// (swf_gftt_detect_batch with one frame and flag bit 0; a caller with many streams builds the same arrays and makes one call).
+//   img                        8-bit grey, rows x cols, dense rows;  mask: the caller's own mask (0 = blocked) or null
+//   cur_pts, ids, track_cnt    the tracker's vectors after rejectWithF and the n++ of track_cnt; on success they are what setMask and
+//                              addPoints leave: the kept points by track_cnt descending (ties by index), then the new corners with
+//                              ids *n_id, *n_id + 1, .. and track_cnt 1
+//   max_cnt, min_dist          MAX_CNT, MIN_DIST
+// Returns true when the call succeeded and the frame is SWF_GFTT_OK.  More candidates than cand_cap (SWF_GFTT_TOO_MANY) makes one more
+// call with the count the first one reported.  On failure (a non-finite position, a negative track_cnt, no device) the state is
+// left as it was.  The declared differences from OpenCV are those of swf_gftt_detect_batch.
+struct DetectFeaturesResult {
+    int info = -1, n_old = 0, n_new = 0, n_cand = 0;
+    double max_eig = 0.0;
+    std::vector<int32_t> why;                           // per point of the state as it came in
+};
+template <class Pts>
+inline bool DetectFeatures(const uint8_t* img, int rows, int cols, Pts* cur_pts, std::vector<int>* ids, std::vector<int>* track_cnt, int* n_id,
+                           DetectFeaturesResult* out, int max_cnt = 350, int min_dist = 30, const uint8_t* mask = nullptr, int cand_cap = 1 << 15) {
+    if (!out || !cur_pts || !ids || !track_cnt || !n_id || ids->size() != cur_pts->size() || track_cnt->size() != cur_pts->size()) return false;
+    const int32_t n = (int32_t)cur_pts->size(), first[2] = { 0, n };
+    std::vector<double> p((size_t)(n + 1) * 2, 0.0), fresh((size_t)(max_cnt > 0 ? max_cnt : 1) * 2, 0.0);
+    std::vector<int32_t> tc((size_t)n + 1, 0), order((size_t)n + 1, -1), why((size_t)n + 1, 0);
+    for (int32_t i = 0; i < n; i++) {
+        p[(size_t)i * 2] = (*cur_pts)[(size_t)i].x; p[(size_t)i * 2 + 1] = (*cur_pts)[(size_t)i].y;
+        tc[(size_t)i] = (*track_cnt)[(size_t)i];
+    }
+    int32_t info = -1, n_old = 0, n_new = 0, n_cand = 0;
+    double max_eig = 0.0;
+    int rc = SWF_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        rc = swf_gftt_detect_batch(1, rows, cols, img, mask, first, p.data(), tc.data(), max_cnt, min_dist, 0.01, nullptr, cand_cap, 1, order.data(), why.data(),
+                                   &n_old, fresh.data(), &n_new, &n_cand, &max_eig, nullptr, nullptr, nullptr, &info, nullptr, 0, nullptr);
+        if (rc != SWF_OK || info != SWF_GFTT_TOO_MANY) break;
+        cand_cap = n_cand;
+    }
+    const bool ok = rc == SWF_OK && info == SWF_GFTT_OK;
+    out->info = rc == SWF_OK ? info : -1;
+    out->n_old = ok ? n_old : 0; out->n_new = ok ? n_new : 0; out->n_cand = rc == SWF_OK && info != SWF_GFTT_BAD_INPUT ? n_cand : 0; out->max_eig = ok ? max_eig : 0.0;
+    why.resize(ok ? (size_t)n : 0);
+    out->why = why;
+    if (!ok) return false;
+    Pts pts;
+    std::vector<int> new_ids, new_cnt;
+    for (int32_t j = 0; j < n_old; j++) {                 // setMask: the kept points in walk order
+        const size_t i = (size_t)order[(size_t)j];
+        pts.push_back((*cur_pts)[i]); new_ids.push_back((*ids)[i]); new_cnt.push_back((*track_cnt)[i]);
+    }
+    for (int32_t j = 0; j < n_new; j++) {                 // addPoints
+        typename Pts::value_type q = typename Pts::value_type();
+        q.x = (float)fresh[(size_t)j * 2]; q.y = (float)fresh[(size_t)j * 2 + 1];
+        pts.push_back(q); new_ids.push_back((*n_id)++); new_cnt.push_back(1);
+    }
+    *cur_pts = pts; *ids = new_ids; *track_cnt = new_cnt;
+    return true;
 }
 
 // what the reference's reduceVector (:21-35) does with a status: the kept elements move to the front, in order

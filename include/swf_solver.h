@@ -727,8 +727,8 @@ int swf_track_reject_batch(int32_t n_pairs, const int32_t* first, const double* 
  * Lucas-Kanade pass (cv::calcOpticalFlowPyrLK, 21 x 21, 3 levels), a reverse pass with 1 level started from the previous positions
  * (FLOW_BACK), the 0.5 px forward-backward gate, inBorder and reduceVector.  It is OpenCV's LKTrackerInvoker restated, with one
  * declared difference: OpenCV accumulates A and b in float in SIMD order; here they are exact integer sums converted once to double,
- * so the float64 referee of the tests is met bit for bit.  Not here: goodFeaturesToTrack, setMask, the id / track_cnt bookkeeping,
- * setPrediction, the stereo branch.  The specification; positions are (x, y), floor is towards -inf, rint to nearest even,
+ * so the float64 referee of the tests is met bit for bit.  Not here: the n++ of track_cnt, setPrediction, the stereo branch (setMask,
+ * goodFeaturesToTrack and addPoints: swf_gftt_detect_batch below).  The specification; positions are (x, y), floor is towards -inf, rint to nearest even,
  * descale(v, n) = (v + 2^(n-1)) >> n arithmetically, r101(i, n) = |i|, and 2 (n - 1) - i above n - 1:
  *   pyramid    level l + 1 has size ((w + 1) / 2, (h + 1) / 2); dst(x, y) = (sum_ij k_i k_j src(r101(2x + i - 2, w), r101(2y + j - 2, h))
  *              + 128) >> 8, k = 1 4 6 4 1.  Building stops before a level whose width or height would be <= win; the level count
@@ -797,6 +797,75 @@ int swf_klt_track_batch(int32_t n_pairs, int32_t rows, int32_t cols, const uint8
                         double back_dist, int32_t flags,
                         double* cur_px, double* back_px, uint8_t* status, int32_t* why, int32_t* keep_idx, int32_t* n_keep,
                         int32_t* info, int32_t* trace_iters, double* trace_px, uint8_t* pyr, int32_t on_device, void* stream);
+
+/* Input producer: the points to track — setMask, cv::goodFeaturesToTrack(cur_img, n_pts, MAX_CNT - cur_pts.size(), 0.01, MIN_DIST, mask)
+ * and addPoints of FeatureTracker::trackImage (R/feature/feature_tracker.cpp:148-165, :44-79) for n_frames independent frames.  It is
+ * OpenCV's goodFeaturesToTrack (blockSize 3, Sobel aperture 3, useHarris false) behind the reference's setMask, restated with the
+ * declared differences below.  The specification; positions are (x, y), rint and r101(i, n) as for swf_klt_track_batch,
+ * r = min_dist:
+ *   A setMask  per frame, c_i = (rint(x_i), rint(y_i)); the tracked points are walked by track_cnt descending, then index ascending.
+ *              c_i outside [0, cols) x [0, rows): why = OUTSIDE, dropped.  c_i not free: why = CROWDED, dropped.  Otherwise KEPT, and
+ *              disc(c_i) is blocked from then on.  free(p): the caller's mask byte at p is non-zero (when a mask is given) and p lies in
+ *              no disc of a kept point.  disc(c) = { (x, y) : |y - c.y| <= r, |x - c.x| <= hw[|y - c.y|] }; with disc_halfwidth null
+ *              hw[d] = floor(sqrt(r^2 - d^2)), an exact integer square root.  No mask image is rasterised on the device.
+ *   B eig      every pixel, P read through r101: Ix = (P(x+1,y-1) - P(x-1,y-1)) + 2 (P(x+1,y) - P(x-1,y)) + (P(x+1,y+1) - P(x-1,y+1)),
+ *              Iy the transposed stencil; A = sum Ix^2, B = sum Ix Iy, C = sum Iy^2 over the 3 x 3 neighbourhood, its positions
+ *              through r101 (the products are reflected, as cv::boxFilter does); D = (A - C)^2 + 4 B^2;
+ *              eig = ((double)(A + C) - sqrt((double)D)) / 18727200.0  (OpenCV's scale 1 / (255 * 4 * 3) squared, the halves folded in).
+ *   exactness  |Ix| <= 1020, A <= 9 363 600 < 2^24, D < 2^49: everything up to D is an exact integer; then one subtraction, one
+ *              correctly rounded square root and one division, each rounded once, no contraction.  D <= (A + C)^2, so eig >= 0.
+ *   C cand     m = max of eig over the free pixels of the whole image; no free pixel or m = 0: no candidates.  t(p) = eig(p) if
+ *              eig(p) > quality * m (one double product), else 0.  p is a candidate iff 1 <= x <= cols - 2 and 1 <= y <= rows - 2,
+ *              t(p) != 0, t(p) >= t of its eight neighbours (blocked neighbours count: OpenCV's dilation does not look at the
+ *              mask), and free(p).
+ *   D select   the candidates are walked by t descending, then by linear index y * cols + x descending (OpenCV's greaterThanPtr); a
+ *              candidate is kept iff every new point kept before it has dx^2 + dy^2 >= r^2; the walk ends at budget = max_cnt - n_old.
+ *              A budget <= 0 skips B to D (n_new = n_cand = 0, max_eig = 0, eig not written).  New points are kept away from old
+ *              ones through free() only, as in the reference.
+ * Declared differences from OpenCV and the reference: (1) OpenCV forms the derivatives, products, box sums and the eigenvalue in float;
+ * here they are exact integers and one double expression, so the operator is not OpenCV bit for bit — it is its own float64 referee
+ * (tests/np_gftt.py) bit for bit.  (2) cv::circle's filled raster is replaced by the half-width table; the default is the Euclidean
+ * disc, and a caller who wants OpenCV's midpoint raster passes its row half-widths (the values are used as they are: a negative one
+ * blocks nothing in its rows).  (3) The reference's std::sort leaves equal track_cnt in unspecified order; here ties go by index.
+ * (4) The reference reads mask.at out of range for a point outside the image; here the point is dropped.
+ * Arrays:
+ *   img        [n_frames][rows][cols]      8-bit grey, dense rows;  mask alike or null: the caller's own mask, 0 = blocked
+ *   first      [n_frames + 1]              offsets of the tracked points;  px [..][2], track_cnt [..] after the caller's n++
+ *   max_cnt, min_dist, quality             the reference's 350, 30, 0.01;  disc_halfwidth [min_dist + 1] or null
+ *   cand_cap                               candidates a frame's workspace can hold
+ *   flags      bit 0: px is rounded through float first, where the reference holds a cv::Point2f
+ *   order      [..]  the kept indices of a frame (counted from its first point) in kept order from first[k], -1 behind them
+ *   why        [..]  SWF_GFTT_KEPT, _OUTSIDE, _CROWDED;  n_old [n_frames]
+ *   new_px     [n_frames][max_cnt][2]      integer-valued, in selection order; entries behind n_new are not written;  n_new [n_frames]
+ *   n_cand, max_eig [n_frames]             the candidates of stage C;  m (0 where there is no free pixel)
+ *   pack_first [n_frames + 1], pack_px [..][2], pack_src [..]: per frame the kept old points' px as given (float-rounded under bit 0)
+ *              in kept order, then the new points; pack_src the index from first[k], -1 for a new point.  pack_first[0] = 0; a frame
+ *              that writes its info only owns an empty range.  Sized for first[n_frames] - first[0] + n_frames * max_cnt points: the
+ *              next call's first / prev_px without a host copy.
+ *   work       [n_frames][swf_gftt_workspace_bytes(rows, cols, cand_cap)], 8-byte aligned: the workspace; a frame's first
+ *              rows * cols doubles are eig, a stage export.  Device memory: required.  Host memory: may be null (staged
+ *              internally); where given, the eig of every SWF_GFTT_OK frame with a budget > 0 is copied back and nothing else.
+ * Every output but info may be null.
+ * info: SWF_GFTT_BAD_INPUT (a non-finite coordinate, tested on what is staged, or a negative track_cnt): the frame writes its info
+ * only.  SWF_GFTT_TOO_MANY (more than cand_cap candidates): the frame writes info and the true n_cand only, so the caller can size the
+ * next call.  rows or cols outside 8 .. 8192, max_cnt outside 1 .. 1024, min_dist outside 1 .. 64, cand_cap above 2^24, unknown flag
+ * bits, more than 65535 frames, (host memory) a frame above SWF_GFTT_NMAX tracked points: SWF_E_UNSUPPORTED; null required pointers
+ * (img, first, px, track_cnt, info; work in device memory), quality outside (0, 1], cand_cap below 64, (host memory) a negative or
+ * decreasing `first`: SWF_E_INVALID; all before any launch.  With host memory the BAD_INPUT frames are found before the device is
+ * touched, and a call all of whose frames are BAD_INPUT does not touch it.  Device memory: a frame whose offsets are negative,
+ * decreasing or above SWF_GFTT_NMAX reports info = -1 and writes nothing else.  A frame's result does not depend on the other frames of
+ * the call (pack_first alone counts the frames in front), and a rerun gives the same bits.  on_device as for swf_preintegrate_batch.
+ * Six launches on the caller's stream, whatever the arguments. */
+enum { SWF_GFTT_OK = 0, SWF_GFTT_BAD_INPUT = 1, SWF_GFTT_TOO_MANY = 2 };   /* per frame */
+enum { SWF_GFTT_KEPT = 0, SWF_GFTT_OUTSIDE = 1, SWF_GFTT_CROWDED = 2 };    /* per tracked point: why */
+#define SWF_GFTT_NMAX 1024  /* tracked points per frame, and max_cnt */
+size_t swf_gftt_workspace_bytes(int32_t rows, int32_t cols, int32_t cand_cap);    /* host only: workspace per FRAME; 0 outside the limits */
+int swf_gftt_detect_batch(int32_t n_frames, int32_t rows, int32_t cols, const uint8_t* img, const uint8_t* mask,
+                          const int32_t* first, const double* px, const int32_t* track_cnt,
+                          int32_t max_cnt, int32_t min_dist, double quality, const int32_t* disc_halfwidth, int32_t cand_cap, int32_t flags,
+                          int32_t* order, int32_t* why, int32_t* n_old, double* new_px, int32_t* n_new, int32_t* n_cand, double* max_eig,
+                          int32_t* pack_first, double* pack_px, int32_t* pack_src, int32_t* info, uint8_t* work,
+                          int32_t on_device, void* stream);
 
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).

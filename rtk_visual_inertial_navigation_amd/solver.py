@@ -66,6 +66,7 @@ EXPORTED = [
     "swf_pnp_frame_batch",
     "swf_track_reject_batch",
     "swf_klt_track_batch", "swf_klt_pyramid_bytes",
+    "swf_gftt_detect_batch", "swf_gftt_workspace_bytes",
 ]
 
 
@@ -1092,6 +1093,78 @@ def klt_track_batch(prev_img, cur_img, prev_px, guess_px=None, win=21, max_level
         out[key] = out[key][:tot]
     if stages:
         out["pyr"] = out["pyr"][:, :nb]
+    return out
+
+
+GFTT_OK, GFTT_BAD_INPUT, GFTT_TOO_MANY = 0, 1, 2
+GFTT_KEPT, GFTT_OUTSIDE, GFTT_CROWDED = 0, 1, 2
+GFTT_NMAX = 1024
+
+
+def gftt_workspace_bytes(rows, cols, cand_cap):
+    """swf_gftt_workspace_bytes: the workspace of one frame (eig first); 0 outside the limits"""
+    fn = lib().swf_gftt_workspace_bytes
+    fn.restype = C.c_size_t
+    return int(fn(C.c_int32(rows), C.c_int32(cols), C.c_int32(cand_cap)))
+
+
+def gftt_detect_batch(img, px, track_cnt, mask=None, max_cnt=350, min_dist=30, quality=0.01, disc_halfwidth=None, cand_cap=1 << 15, flags=1,
+                      fill=0.0, stages=False):
+    """setMask, cv::goodFeaturesToTrack and addPoints of FeatureTracker::trackImage (R/feature/feature_tracker.cpp:148-165) for a batch
+    of frames on the device (swf_gftt_detect_batch).  img (and mask, 0 = blocked): [n][rows][cols] uint8; px, track_cnt: lists of the
+    frames' tracked points [n_k][2] (x, y) and their counts [n_k]; disc_halfwidth: [min_dist + 1] row half-widths of the blocked disc
+    (None: the Euclidean disc); flags bit 0: px through float.  Returns dict(order, why, first, n_old, new_px [n][max_cnt][2], n_new,
+    n_cand, max_eig, pack_first, pack_px, pack_src, info) and, with stages=True, eig [n][rows][cols]; order and why are [first[n]],
+    frame k owning first[k] .. first[k + 1]; pack_px and pack_src are cut to pack_first[n].  What a frame does not write stays at
+    `fill` (the integer outputs at int(fill))."""
+    im = np.ascontiguousarray(img, dtype=np.uint8)
+    if im.ndim != 3:
+        raise SwfError("gftt_detect_batch: the images must be one [n][rows][cols] array")
+    n, rows, cols = im.shape
+    mk = None
+    if mask is not None:
+        mk = np.ascontiguousarray(mask, dtype=np.uint8)
+        if mk.shape != im.shape:
+            raise SwfError("gftt_detect_batch: the mask does not match the images")
+    pp = [np.asarray(p, np.float64).reshape(-1, 2) for p in px]
+    tc = [np.asarray(t, np.int32).reshape(-1) for t in track_cnt]
+    if len(pp) != n or [p.shape[0] for p in pp] != [t.size for t in tc]:
+        raise SwfError("gftt_detect_batch: %d frames, %d point sets and %d count sets, or sets of different lengths" % (n, len(pp), len(tc)))
+    first = np.zeros(n + 1, np.int32)
+    for i in range(n):
+        first[i + 1] = first[i] + pp[i].shape[0]
+    tot = int(first[n])
+    fp = np.ascontiguousarray(np.concatenate(pp + [np.zeros((1, 2))]))
+    ft = np.ascontiguousarray(np.concatenate(tc + [np.zeros(1, np.int32)]))
+    hw = None if disc_halfwidth is None else np.ascontiguousarray(disc_halfwidth, dtype=np.int32)
+    if hw is not None and hw.size != min_dist + 1:
+        raise SwfError("gftt_detect_batch: disc_halfwidth needs min_dist + 1 entries")
+    pts, mc, ifill = max(tot, 1), max(int(max_cnt), 1), int(fill)
+    npack = tot + n * mc + 1
+    out = dict(order=np.full(pts, ifill, np.int32), why=np.full(pts, ifill, np.int32), first=first, n_old=np.full(n, ifill, np.int32),
+               new_px=np.full((n, mc, 2), float(fill)), n_new=np.full(n, ifill, np.int32), n_cand=np.full(n, ifill, np.int32),
+               max_eig=np.full(n, float(fill)), pack_first=np.full(n + 1, ifill, np.int32), pack_px=np.full((npack, 2), float(fill)),
+               pack_src=np.full(npack, ifill, np.int32), info=np.full(n, -1, np.int32))
+    pi, pb = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    work = None
+    if stages:
+        wb = gftt_workspace_bytes(rows, cols, cand_cap)
+        work = np.zeros((n, max(wb, rows * cols * 8)), np.uint8)
+        work[:, :rows * cols * 8].view(np.float64)[...] = float(fill)
+    _chk(lib().swf_gftt_detect_batch(C.c_int32(n), C.c_int32(rows), C.c_int32(cols), im.ctypes.data_as(pb), mk.ctypes.data_as(pb) if mk is not None else None,
+                                     first.ctypes.data_as(pi), fp.ctypes.data_as(_pd), ft.ctypes.data_as(pi), C.c_int32(max_cnt), C.c_int32(min_dist),
+                                     C.c_double(quality), hw.ctypes.data_as(pi) if hw is not None else None, C.c_int32(cand_cap), C.c_int32(flags),
+                                     out["order"].ctypes.data_as(pi), out["why"].ctypes.data_as(pi), out["n_old"].ctypes.data_as(pi),
+                                     out["new_px"].ctypes.data_as(_pd), out["n_new"].ctypes.data_as(pi), out["n_cand"].ctypes.data_as(pi),
+                                     out["max_eig"].ctypes.data_as(_pd), out["pack_first"].ctypes.data_as(pi), out["pack_px"].ctypes.data_as(_pd),
+                                     out["pack_src"].ctypes.data_as(pi), out["info"].ctypes.data_as(pi),
+                                     work.ctypes.data_as(pb) if work is not None else None, C.c_int32(0), None), "gftt_detect_batch")
+    for key in ("order", "why"):
+        out[key] = out[key][:tot]
+    used = int(out["pack_first"][n]) if out["pack_first"][n] >= 0 and (out["info"] != GFTT_BAD_INPUT).any() else 0
+    out["pack_px"], out["pack_src"] = out["pack_px"][:used], out["pack_src"][:used]
+    if stages:
+        out["eig"] = work[:, :rows * cols * 8].view(np.float64).reshape(n, rows, cols)
     return out
 
 
