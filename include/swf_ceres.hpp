@@ -31,15 +31,18 @@
 //   rejectWithF() + undistortedPts() + ptsVelocity()  R/feature/feature_tracker.cpp:265-294, :334-376 -> swf_track_reject_batch (RejectWithF below)
 //   trackImage(): calcOpticalFlowPyrLK forward + reverse, the 0.5 px gate, inBorder   R/feature/feature_tracker.cpp:98-141 -> swf_klt_track_batch (TrackImageKLT below)
 //   trackImage(): setMask() + cv::goodFeaturesToTrack + addPoints()   R/feature/feature_tracker.cpp:148-165, :44-79 -> swf_gftt_detect_batch (DetectFeatures below)
+//   FeatureTracker::trackImage() + removeOutliers(), the state from frame to frame   R/feature/feature_tracker.cpp:88-263 -> swf_tracker_* (FeatureTracker below)
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -1102,5 +1105,65 @@ inline void ReduceVector(std::vector<T>& v, const std::vector<uint8_t>& status) 
     }
     v.resize(kept);
 }
+
+// The whole tracker: FeatureTracker::trackImage (R/feature/feature_tracker.cpp:88-263) and removeOutliers for one camera, its state
+// (prev_img, prev_pts, ids, track_cnt, n_id, the previous normalised points, prev_time) resident on the device (swf_tracker_* with one
+// stream; a caller with many cameras or sequences creates one swf_tracker with as many streams and makes one call per frame).  The
+// three stages above run chained in device memory; nothing but the image goes up and the feature frame comes down.
+//   FeatureTracker(rows, cols, cam, options)   cam = fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6; options: null for the reference's values
+//   trackImage(t, img)                         the reference's featureFrame: feature id -> [(camera id 0, x y 1 u v vx vy)]; a failed
+//                                              call (last_rc != SWF_OK) returns an empty map
+//   removeOutliers(ids)                        as the reference
+// info and counts of the last frame are the words of swf_tracker_download.  setPrediction, the stereo branch and drawTrack are not
+// covered.  The seed of the F gate's sampling is the frame number, so a sequence is reproducible.
+class FeatureTracker {
+public:
+    typedef std::map<int, std::vector<std::pair<int, std::array<double, 7>>>> FeatureFrame;
+    FeatureTracker(int rows, int cols, const double cam[12], const swf_tracker_options* options = nullptr) {
+        swf_tracker_options o;
+        swf_tracker_default_options(&o);
+        if (options) o = *options;
+        max_cnt_ = o.max_cnt;
+        last_rc = swf_tracker_create(1, rows, cols, cam, &o, nullptr, &t_);
+    }
+    ~FeatureTracker() { swf_tracker_destroy(t_); }
+    FeatureTracker(const FeatureTracker&) = delete;
+    FeatureTracker& operator=(const FeatureTracker&) = delete;
+
+    FeatureFrame trackImage(double cur_time, const uint8_t* img, const uint8_t* mask = nullptr) {
+        FeatureFrame frame;
+        if (!t_) return frame;
+        last_rc = swf_tracker_track(t_, &cur_time, img, mask, (uint64_t)n_frames_, 0);
+        if (last_rc != SWF_OK) return frame;
+        n_frames_++;
+        const size_t cap = (size_t)(max_cnt_ > 0 ? max_cnt_ : 1);
+        int32_t n = 0;
+        ids.assign(cap, 0); track_cnt.assign(cap, 0);
+        std::vector<double> obs(cap * 7, 0.0);
+        last_rc = swf_tracker_download(t_, &n, ids.data(), track_cnt.data(), obs.data(), counts, &info);
+        if (last_rc != SWF_OK) n = 0;
+        ids.resize((size_t)n); track_cnt.resize((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            std::array<double, 7> v;
+            for (int k = 0; k < 7; k++) v[(size_t)k] = obs[(size_t)i * 7 + (size_t)k];
+            frame[ids[(size_t)i]].emplace_back(0, v);
+        }
+        return frame;
+    }
+    void removeOutliers(const std::set<int>& removePtsIds) {
+        if (!t_) return;
+        const std::vector<int32_t> list(removePtsIds.begin(), removePtsIds.end());
+        const int32_t first[2] = { 0, (int32_t)list.size() }, none = 0;
+        last_rc = swf_tracker_remove_ids(t_, first, list.empty() ? &none : list.data());
+    }
+
+    int last_rc = SWF_OK;
+    int32_t info = 0, counts[SWF_TRACKER_NCOUNT] = { 0 };
+    std::vector<int32_t> ids, track_cnt;                // of the last frame, in the tracker's order
+private:
+    swf_tracker* t_ = nullptr;
+    int max_cnt_ = 0;
+    long long n_frames_ = 0;
+};
 
 }  // namespace swf_ceres

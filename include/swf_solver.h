@@ -867,6 +867,79 @@ int swf_gftt_detect_batch(int32_t n_frames, int32_t rows, int32_t cols, const ui
                           int32_t* pack_first, double* pack_px, int32_t* pack_src, int32_t* info, uint8_t* work,
                           int32_t on_device, void* stream);
 
+/* The resident feature tracker: FeatureTracker::trackImage (R/feature/feature_tracker.cpp:88-263) and removeOutliers for n_streams
+ * independent image sequences whose state (prev_img, prev_pts, ids, track_cnt, n_id, the previous normalised points, prev_time) stays
+ * on the device.  swf_tracker_track enqueues one frame of every stream on the tracker's stream: the three operators above
+ * through their launchers, unchanged, with the reference's flags (KLT 5, or 1 without flow_back; float rounding bit 0 everywhere),
+ * and between them the bookkeeping kernels of swf_tracker.hip.  It does not synchronise, allocate or copy from the device.
+ * Per stream, in the reference's order:
+ *   1 KLT prev_img -> img from prev_px (not on the tracker's first call: no stream has points); prev_px, cur_px, ids, track_cnt and the
+ *     lineage are gathered by keep_idx, a new `first` is the prefix of n_keep
+ *   2 track_cnt += 1
+ *   3 rejectWithF on the survivors, dt = times[s] - prev_time[s] (1 on a stream's first frame, which has no points), the call's seed;
+ *     gathered by its keep_idx.  SWF_TRK_TOO_FEW keeps all, as the reference.  SWF_TRK_NO_MODEL keeps all and sets SWF_TRACKER_NO_MODEL
+ *     in info: a declared difference (OpenCV leaves status unwritten there and the reference reads it out of range).
+ *   4 setMask, goodFeaturesToTrack, addPoints on img: a kept point carries its id and track_cnt, the j-th new point of the stream gets
+ *     id = n_id + j and track_cnt = 1 in selection order, then n_id += n_new.  SWF_GFTT_TOO_MANY: the stream keeps what setMask kept,
+ *     adds none, sets SWF_TRACKER_TOO_MANY in info and reports the true n_cand in counts.
+ *   5 un = the PINHOLE_FULL lift of the final pixels: swf_track_reject_batch's un_cur for the same pixels, bit for bit
+ *   6 velocity = ptsVelocity: for a point of the previous frame's final list the difference in float, the quotient by dt in double,
+ *     stored as float; (0, 0) for a new point and on a stream's first frame.  The reference's id maps are replaced by a lineage index
+ *     carried through the gathers; ids are unique, so the two agree.
+ *   7 obs = (un.x, un.y, 1, px.x, px.y, v.x, v.y), the float values widened to double
+ *   8 the state rolls; the two image buffers swap as pointers.
+ * counts [n_streams][SWF_TRACKER_NCOUNT]: points in, after KLT, after the F gate, kept by setMask, new, n_cand, final, then the info
+ * words of the KLT (0 where it did not run), track-reject and detection stages.  info [n_streams]: the SWF_TRACKER_* bits;
+ * SWF_TRACKER_STAGE_FAILED marks a stage info no valid state can produce (BAD_INPUT, -1): that stage then keeps every point.
+ * A stream's result does not depend on the other streams, a rerun from the same state gives the same bits, and the number of launches
+ * depends on the options and on whether it is the first call, never on the data: 3 bookkeeping kernels, 6 of the detector, 1 of the
+ * gate and, from the second call on, max(max_level, back_level) + 2 of the KLT.
+ * swf_tracker_create allocates everything (two image buffers, the mask, the KLT pyramids, the detector workspace, max_cnt slots of
+ * state per stream, the inter-stage arrays).  Refused before the device is touched, as by the operators it wraps: null cam, opt or
+ * out, non-finite or non-positive eps, min_eig, back_dist, f_threshold, focal, non-finite f_confidence or cam, fx or fy of 0, quality
+ * outside (0, 1], cand_cap below 64: SWF_E_INVALID; n_streams outside 1 .. 65535, win even or outside 3 .. 21, rows or cols <= win,
+ * below 8 or above 8192, levels outside 0 .. 4, max_count outside 1 .. 1000, max_cnt outside 1 .. SWF_GFTT_NMAX, min_dist outside
+ * 1 .. 64, cand_cap above 2^24, f_iterations outside 1 .. SWF_TRK_HMAX, negative virt_col or virt_row: SWF_E_UNSUPPORTED.
+ * swf_tracker_track: times is host memory; img is [n_streams][rows][cols] in host memory, or device memory with img_on_device (then
+ * mask too); a host image is copied in with hipMemcpyAsync on the tracker's stream.  Null t, times or img, a non-finite time or one
+ * not strictly above the stream's previous time: SWF_E_INVALID before any launch, the state untouched.
+ * swf_tracker_remove_ids is removeOutliers: the ids[first[s] .. first[s + 1]) leave stream s's prev_px, ids and track_cnt, order
+ * preserved; an id that is not there is ignored; the previous normalised points stay.  More than max_cnt ids for a stream:
+ * SWF_E_UNSUPPORTED; a negative or decreasing first, null pointers: SWF_E_INVALID.  Two launches, no synchronisation.
+ * swf_tracker_download synchronises and copies the frame the last swf_tracker_track produced (a later remove_ids shows in the next
+ * frame): n [n_streams], and ids, track_cnt, obs [..][7] packed stream after stream (at most n_streams * max_cnt points); any pointer
+ * may be null.  SWF_E_STATE before the first track.  swf_tracker_device_frame gives the device pointers of the same frame: first
+ * [n_streams + 1], ids, track_cnt, px [..][2], obs [..][7]; first and px are the first / prev_px of swf_klt_track_batch.
+ * Not covered: setPrediction / hasPrediction (never called in the reference), the stereo branch (USE_STEREO 0 in every shipped
+ * configuration), drawTrack, and streams that skip a frame (every call carries a frame for every stream). */
+typedef struct swf_tracker swf_tracker;
+typedef struct swf_tracker_options {   /* swf_tracker_default_options fills the reference's values */
+    int32_t max_cnt, min_dist;          /* MAX_CNT 350 (<= SWF_GFTT_NMAX), MIN_DIST 30 */
+    double  quality;                    /* 0.01 */
+    int32_t cand_cap;                   /* 1 << 15 */
+    int32_t win, max_level, back_level, max_count;   /* 21, 3, 1, 30 */
+    double  eps, min_eig, back_dist;    /* 0.01, 1e-4, 0.5 */
+    int32_t flow_back;                  /* FLOW_BACK: 1 */
+    int32_t f_iterations; double f_threshold, f_confidence, focal;   /* 1000, F_THRESHOLD 1.0, 0.99, FOCAL_LENGTH 1000 */
+    int32_t virt_col, virt_row;         /* the col / row of rejectWithF's virtual camera: 0 = the image's */
+} swf_tracker_options;
+enum { SWF_TRACKER_NO_MODEL = 1, SWF_TRACKER_TOO_MANY = 2, SWF_TRACKER_STAGE_FAILED = 4 };   /* info bits */
+enum { SWF_TRACKER_C_IN = 0, SWF_TRACKER_C_KLT = 1, SWF_TRACKER_C_F = 2, SWF_TRACKER_C_MASK = 3, SWF_TRACKER_C_NEW = 4, SWF_TRACKER_C_CAND = 5,
+       SWF_TRACKER_C_FINAL = 6, SWF_TRACKER_C_KLT_INFO = 7, SWF_TRACKER_C_TRK_INFO = 8, SWF_TRACKER_C_GFTT_INFO = 9 };
+#define SWF_TRACKER_NCOUNT 10
+void swf_tracker_default_options(swf_tracker_options*);
+int swf_tracker_create(int32_t n_streams, int32_t rows, int32_t cols, const double cam[12], const swf_tracker_options* opt,
+                       void* stream, swf_tracker** out);
+int swf_tracker_track(swf_tracker* t, const double* times /* host, [n_streams] */, const uint8_t* img /* [n_streams][rows][cols] */,
+                      const uint8_t* mask /* or null */, uint64_t seed, int32_t img_on_device);
+int swf_tracker_remove_ids(swf_tracker* t, const int32_t* first /* host, [n_streams + 1] */, const int32_t* ids /* host */);
+int swf_tracker_download(swf_tracker* t, int32_t* n /* [n_streams] */, int32_t* ids, int32_t* track_cnt, double* obs /* [..][7] */,
+                         int32_t* counts /* [n_streams][SWF_TRACKER_NCOUNT] */, int32_t* info /* [n_streams] */);
+int swf_tracker_device_frame(swf_tracker* t, const int32_t** first, const int32_t** ids, const int32_t** track_cnt,
+                             const double** px, const double** obs);   /* device pointers of the current frame, for chaining */
+int swf_tracker_sync(swf_tracker* t);
+int swf_tracker_destroy(swf_tracker* t);
+
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).
  *   Ps [n_frames][3], Rs [n_frames][9] (row-major)  frame positions / rotations as the reference passes them

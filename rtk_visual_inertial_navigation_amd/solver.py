@@ -67,6 +67,8 @@ EXPORTED = [
     "swf_track_reject_batch",
     "swf_klt_track_batch", "swf_klt_pyramid_bytes",
     "swf_gftt_detect_batch", "swf_gftt_workspace_bytes",
+    "swf_tracker_default_options", "swf_tracker_create", "swf_tracker_track", "swf_tracker_remove_ids", "swf_tracker_download",
+    "swf_tracker_device_frame", "swf_tracker_sync", "swf_tracker_destroy",
 ]
 
 
@@ -1166,6 +1168,110 @@ def gftt_detect_batch(img, px, track_cnt, mask=None, max_cnt=350, min_dist=30, q
     if stages:
         out["eig"] = work[:, :rows * cols * 8].view(np.float64).reshape(n, rows, cols)
     return out
+
+
+TRACKER_NO_MODEL, TRACKER_TOO_MANY, TRACKER_STAGE_FAILED = 1, 2, 4
+TRACKER_NCOUNT = 10
+TRACKER_COUNTS = ("in", "klt", "f", "mask", "new", "cand", "final", "klt_info", "trk_info", "gftt_info")
+
+
+class TrackerOptionsC(C.Structure):
+    """swf_tracker_options of include/swf_solver.h"""
+    _fields_ = [("max_cnt", C.c_int32), ("min_dist", C.c_int32), ("quality", C.c_double), ("cand_cap", C.c_int32),
+                ("win", C.c_int32), ("max_level", C.c_int32), ("back_level", C.c_int32), ("max_count", C.c_int32),
+                ("eps", C.c_double), ("min_eig", C.c_double), ("back_dist", C.c_double), ("flow_back", C.c_int32),
+                ("f_iterations", C.c_int32), ("f_threshold", C.c_double), ("f_confidence", C.c_double), ("focal", C.c_double),
+                ("virt_col", C.c_int32), ("virt_row", C.c_int32)]
+
+
+def tracker_options(**options):
+    """the reference's options (swf_tracker_default_options) with the given fields replaced"""
+    o = TrackerOptionsC()
+    lib().swf_tracker_default_options(C.byref(o))
+    names = {f[0] for f in TrackerOptionsC._fields_}
+    for k, v in options.items():
+        if k not in names:
+            raise SwfError("Tracker: unknown option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class Tracker:
+    """FeatureTracker::trackImage and removeOutliers for n_streams image sequences whose state stays on the device (swf_tracker_*).
+    cam [12] = fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6; the options are the fields of swf_tracker_options.  track() enqueues one frame
+    of every stream and returns at once; frame() waits and returns the frame the last track() produced."""
+
+    def __init__(self, n_streams, rows, cols, cam, stream=None, **options):
+        self._h = C.c_void_p()
+        self.n_streams, self.rows, self.cols = int(n_streams), int(rows), int(cols)
+        self.opt = tracker_options(**options)
+        cm = (C.c_double * 12)(*[float(x) for x in np.asarray(cam, np.float64).reshape(12)])
+        _chk(lib().swf_tracker_create(C.c_int32(n_streams), C.c_int32(rows), C.c_int32(cols), cm, C.byref(self.opt),
+                                      C.c_void_p(stream), C.byref(self._h)), "swf_tracker_create")
+
+    def close(self):
+        if self._h:
+            lib().swf_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def track(self, times, imgs, mask=None, seed=0):
+        """times [n_streams]; imgs (and mask, 0 = blocked) [n_streams][rows][cols] uint8 in host memory"""
+        shape = (self.n_streams, self.rows, self.cols)
+        t = np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1))
+        im = np.ascontiguousarray(imgs, dtype=np.uint8)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        if t.size != self.n_streams or im.shape != shape or (mk is not None and mk.shape != shape):
+            raise SwfError("Tracker.track: times, imgs and mask must be [%d], [%d][%d][%d]" % ((self.n_streams,) + shape))
+        pb = C.POINTER(C.c_uint8)
+        _chk(lib().swf_tracker_track(self._h, t.ctypes.data_as(_pd), im.ctypes.data_as(pb), mk.ctypes.data_as(pb) if mk is not None else None,
+                                     C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_int32(0)), "swf_tracker_track")
+
+    def track_device(self, times, d_imgs, d_mask=None, seed=0):
+        """track() for images (and mask) that are device memory already: d_imgs, d_mask are device addresses"""
+        t = np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1))
+        if t.size != self.n_streams:
+            raise SwfError("Tracker.track_device: times must be [%d]" % self.n_streams)
+        _chk(lib().swf_tracker_track(self._h, t.ctypes.data_as(_pd), C.c_void_p(d_imgs), C.c_void_p(d_mask) if d_mask else None,
+                                     C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_int32(1)), "swf_tracker_track")
+
+    def remove_ids(self, ids):
+        """removeOutliers: ids is a list of one id array per stream"""
+        per = [np.asarray(a, np.int32).reshape(-1) for a in ids]
+        if len(per) != self.n_streams:
+            raise SwfError("Tracker.remove_ids: %d id arrays for %d streams" % (len(per), self.n_streams))
+        first = np.concatenate([[0], np.cumsum([a.size for a in per])]).astype(np.int32)
+        flat = np.ascontiguousarray(np.concatenate(per + [np.zeros(1, np.int32)]))
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_tracker_remove_ids(self._h, first.ctypes.data_as(pi), flat.ctypes.data_as(pi)), "swf_tracker_remove_ids")
+
+    def sync(self):
+        _chk(lib().swf_tracker_sync(self._h), "swf_tracker_sync")
+
+    def frame(self):
+        """dict(ids, track_cnt, obs, counts, info): per stream the ids [n], track_cnt [n], obs [n][7] = x y 1 u v vx vy, the
+        counts [TRACKER_NCOUNT] (TRACKER_COUNTS names them) and the info bits of the last tracked frame"""
+        ns, cap = self.n_streams, self.n_streams * self.opt.max_cnt
+        n = np.zeros(ns, np.int32)
+        ids, tc, obs = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros((cap, 7))
+        counts, info = np.zeros((ns, TRACKER_NCOUNT), np.int32), np.zeros(ns, np.int32)
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_tracker_download(self._h, n.ctypes.data_as(pi), ids.ctypes.data_as(pi), tc.ctypes.data_as(pi), obs.ctypes.data_as(_pd),
+                                        counts.ctypes.data_as(pi), info.ctypes.data_as(pi)), "swf_tracker_download")
+        first = np.concatenate([[0], np.cumsum(n)])
+        cut = lambda a: [a[first[s]:first[s + 1]].copy() for s in range(ns)]
+        return dict(ids=cut(ids), track_cnt=cut(tc), obs=cut(obs), counts=[counts[s].copy() for s in range(ns)], info=[int(v) for v in info])
+
+    def device_frame(self):
+        """the device addresses of the last frame's first, ids, track_cnt, px, obs (swf_tracker_device_frame)"""
+        p = [C.c_void_p() for _ in range(5)]
+        _chk(lib().swf_tracker_device_frame(self._h, *[C.byref(v) for v in p]), "swf_tracker_device_frame")
+        return dict(zip(("first", "ids", "track_cnt", "px", "obs"), [v.value for v in p]))
 
 
 def triangulate_batch(Ps, Rs, tic, ric, pbg, start_frame, pt0, pt1, init_depth=5.0):
