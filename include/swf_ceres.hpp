@@ -32,6 +32,8 @@
 //   trackImage(): calcOpticalFlowPyrLK forward + reverse, the 0.5 px gate, inBorder   R/feature/feature_tracker.cpp:98-141 -> swf_klt_track_batch (TrackImageKLT below)
 //   trackImage(): setMask() + cv::goodFeaturesToTrack + addPoints()   R/feature/feature_tracker.cpp:148-165, :44-79 -> swf_gftt_detect_batch (DetectFeatures below)
 //   FeatureTracker::trackImage() + removeOutliers(), the state from frame to frame   R/feature/feature_tracker.cpp:88-263 -> swf_tracker_* (FeatureTracker below)
+//   FeatureManager: addFeatureCheckParallax() removeOut() triangulate() removeFailures() CheckParallax() removeBack() removeFront()
+//                                               R/feature/feature_manager.cpp         -> swf_ftable_* (FeatureManager below)
 //   ceres::internal::{parameter_head,is_optimize,lhs_out,rhs_out,lhs_out2,hs_row}
 //                                               R/swf/swf_gnss.cpp:25-94              -> swf_ceres::internal::* below
 #pragma once
@@ -1164,6 +1166,141 @@ private:
     swf_tracker* t_ = nullptr;
     int max_cnt_ = 0;
     long long n_frames_ = 0;
+};
+
+// The track table: FeatureManager (R/feature/feature_manager.cpp) for one window, resident on the device (swf_ftable_* with one
+// stream; a caller with many windows creates one swf_ftable with as many streams).  World-point mode (USE_INVERSE_DEPTH 0),
+// no stereo.  Poses are plain arrays by image frame: Ps [window][3], Rs [window][9] row-major; tic [3], ric [9] row-major, pbg [3].
+//   addFeatureCheckParallax(image_index, image)   takes FeatureTracker's featureFrame; image_index must be the table's frame count.
+//                                                 removeOut runs in the same enqueue, so removeOut() itself has nothing left to do
+//   pnpPoints(pts_w, pts_uv)                      the gather of initFramePoseByPnP, the input of InitFramePoseByPnP above
+//   triangulate(Ps, Rs, tic, ric, pbg)            the two-view branch, bit-identical to swf_triangulate_batch
+//   listFeatures(L)                               AddFeature2Problem as data (Listing below); setSolved() takes the solve's points back
+//   removeFailures()                              returns the erased ids: the argument of FeatureTracker::removeOutliers
+//   CheckParallax(image_index), removeBack(P0, R0, P1, R1, tic, ric, pbg), removeFront(image_index), ClearState(), getFeatureCount()
+// counts are the words of swf_ftable_counts after the last call that read them; info is counts[SWF_FTABLE_C_INFO].
+class FeatureManager {
+public:
+    struct Listing {
+        std::vector<int32_t> lm_id, lm_start, lm_nobs, lm_valid, proj_frame, proj_lm, proj_new;
+        std::vector<double> lm_world, proj_uv;          // [..][3], [..][2]
+    };
+    explicit FeatureManager(const swf_ftable_options* options = nullptr) {
+        swf_ftable_default_options(&opt_);
+        if (options) opt_ = *options;
+        last_rc = swf_ftable_create(1, &opt_, nullptr, &t_);
+    }
+    ~FeatureManager() { swf_ftable_destroy(t_); }
+    FeatureManager(const FeatureManager&) = delete;
+    FeatureManager& operator=(const FeatureManager&) = delete;
+
+    void ClearState() { if (t_) last_rc = swf_ftable_clear(t_); }
+    bool addFeatureCheckParallax(int image_index, const FeatureTracker::FeatureFrame& image) {
+        if (!t_) return true;
+        std::vector<int32_t> ids;
+        std::vector<double> obs;
+        for (const auto& id_pts : image) {
+            if (id_pts.second.empty()) continue;
+            ids.push_back(id_pts.first);
+            for (int k = 0; k < 7; k++) obs.push_back(id_pts.second[0].second[(size_t)k]);
+        }
+        const int32_t first[2] = { 0, (int32_t)ids.size() }, none = 0;
+        const double zero[7] = { 0, 0, 0, 0, 0, 0, 0 };
+        last_rc = swf_ftable_add_frame(t_, first, ids.empty() ? &none : ids.data(), obs.empty() ? zero : obs.data(), 0);
+        if (last_rc == SWF_OK) fetch();
+        last_track_num = counts[SWF_FTABLE_C_LAST_TRACK]; long_track_num = counts[SWF_FTABLE_C_LONG_TRACK];
+        new_feature_num = counts[SWF_FTABLE_C_NEW];
+        (void)image_index;
+        return last_rc != SWF_OK || counts[SWF_FTABLE_C_KEYFRAME] != 0;
+    }
+    void removeOut(int /*windowsize*/) {}
+    bool CheckParallax(int /*image_index*/) {
+        if (!t_) return true;
+        last_rc = swf_ftable_check_parallax(t_);
+        if (last_rc == SWF_OK) fetch();
+        last_average_parallax = parallax_;
+        return last_rc != SWF_OK || counts[SWF_FTABLE_C_KEYFRAME] != 0;
+    }
+    void pnpPoints(std::vector<double>& pts_w, std::vector<double>& pts_uv) {
+        pts_w.clear(); pts_uv.clear();
+        if (!t_) return;
+        const int32_t* f = nullptr; const double* w = nullptr; const double* uv = nullptr;
+        int32_t first[2] = { 0, 0 };
+        last_rc = swf_ftable_pnp_points(t_, &f, &w, &uv);
+        if (last_rc == SWF_OK) last_rc = swf_ftable_fetch(t_, first, f, sizeof(first));
+        if (last_rc != SWF_OK || first[1] <= 0) return;
+        pts_w.resize((size_t)first[1] * 3); pts_uv.resize((size_t)first[1] * 2);
+        last_rc = swf_ftable_fetch(t_, pts_w.data(), w, pts_w.size() * sizeof(double));
+        if (last_rc == SWF_OK) last_rc = swf_ftable_fetch(t_, pts_uv.data(), uv, pts_uv.size() * sizeof(double));
+    }
+    void triangulate(const double* Ps, const double* Rs, const double tic[3], const double ric[9], const double pbg[3]) {
+        if (t_) last_rc = swf_ftable_triangulate(t_, Ps, Rs, tic, ric, pbg, 0);
+    }
+    void listFeatures(Listing& L) {
+        L = Listing();
+        if (!t_) return;
+        swf_ftable_listing d;
+        int32_t lf[2] = { 0, 0 }, pf[2] = { 0, 0 };
+        last_rc = swf_ftable_list(t_, &d);
+        if (last_rc == SWF_OK) last_rc = swf_ftable_fetch(t_, lf, d.lm_first, sizeof(lf));
+        if (last_rc == SWF_OK) last_rc = swf_ftable_fetch(t_, pf, d.proj_first, sizeof(pf));
+        if (last_rc != SWF_OK) return;
+        const size_t n = (size_t)(lf[1] > 0 ? lf[1] : 0), m = (size_t)(pf[1] > 0 ? pf[1] : 0);
+        auto ints = [&](std::vector<int32_t>& v, const int32_t* src, size_t k) { v.resize(k); if (k && last_rc == SWF_OK) last_rc = swf_ftable_fetch(t_, v.data(), src, k * sizeof(int32_t)); };
+        auto reals = [&](std::vector<double>& v, const double* src, size_t k) { v.resize(k); if (k && last_rc == SWF_OK) last_rc = swf_ftable_fetch(t_, v.data(), src, k * sizeof(double)); };
+        ints(L.lm_id, d.lm_id, n); ints(L.lm_start, d.lm_start, n); ints(L.lm_nobs, d.lm_nobs, n); ints(L.lm_valid, d.lm_valid, n);
+        reals(L.lm_world, d.lm_world, n * 3);
+        ints(L.proj_frame, d.proj_frame, m); ints(L.proj_lm, d.proj_lm, m); ints(L.proj_new, d.proj_new, m);
+        reals(L.proj_uv, d.proj_uv, m * 2);
+    }
+    int getFeatureCount() {                             // the features a listing would hold; in_problem is not touched
+        if (!t_) return 0;
+        std::vector<int32_t> n((size_t)opt_.feat_cap, 0);
+        int32_t n_feat = 0;
+        last_rc = swf_ftable_download(t_, nullptr, &n_feat, nullptr, nullptr, n.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        int cnt = 0;
+        for (int32_t i = 0; last_rc == SWF_OK && i < n_feat; i++) cnt += n[(size_t)i] >= opt_.feature_continue ? 1 : 0;
+        return cnt;
+    }
+    // lm_world [n][3] in the order of the last listFeatures; flags [n] (swf_batch_get_feature_check's) or null
+    void setSolved(const std::vector<double>& lm_world, const uint8_t* flags, const double* Ps, const double* Rs, const double tic[3],
+                   const double ric[9], const double pbg[3]) {
+        if (!t_) return;
+        const int32_t first[2] = { 0, (int32_t)(lm_world.size() / 3) };
+        const double zero[3] = { 0, 0, 0 };
+        last_rc = swf_ftable_set_solved(t_, first, lm_world.empty() ? zero : lm_world.data(), flags, Ps, Rs, tic, ric, pbg, 0);
+    }
+    std::set<int> removeFailures() {
+        std::set<int> gone;
+        if (!t_) return gone;
+        last_rc = swf_ftable_remove_failures(t_, nullptr, nullptr);
+        int32_t first[2] = { 0, 0 };
+        std::vector<int32_t> ids((size_t)opt_.feat_cap, 0);
+        if (last_rc == SWF_OK) last_rc = swf_ftable_removed(t_, first, ids.data());
+        for (int32_t i = 0; last_rc == SWF_OK && i < first[1]; i++) gone.insert(ids[(size_t)i]);
+        return gone;
+    }
+    void removeBack(const double P0[3], const double R0[9], const double P1[3], const double R1[9], const double tic[3], const double ric[9],
+                    const double pbg[3]) {
+        const int32_t mode = 1;
+        if (t_) last_rc = swf_ftable_slide(t_, &mode, P0, R0, P1, R1, tic, ric, pbg, 0);
+    }
+    void removeFront(int /*image_index*/) {
+        const int32_t mode = 2;
+        const double z3[3] = { 0, 0, 0 }, eye[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+        if (t_) last_rc = swf_ftable_slide(t_, &mode, nullptr, nullptr, z3, eye, z3, eye, z3, 0);
+    }
+    swf_ftable* handle() { return t_; }
+
+    int last_rc = SWF_OK;
+    int last_track_num = 0, new_feature_num = 0, long_track_num = 0;
+    double last_average_parallax = 0.0;
+    int32_t counts[SWF_FTABLE_NCOUNT] = { 0 };
+private:
+    void fetch() { last_rc = swf_ftable_counts(t_, counts, &parallax_); }
+    swf_ftable* t_ = nullptr;
+    swf_ftable_options opt_;
+    double parallax_ = 0.0;
 };
 
 }  // namespace swf_ceres

@@ -940,6 +940,111 @@ int swf_tracker_device_frame(swf_tracker* t, const int32_t** first, const int32_
 int swf_tracker_sync(swf_tracker* t);
 int swf_tracker_destroy(swf_tracker* t);
 
+/* The resident feature table: FeatureManager (R/feature/feature_manager.cpp) as ImagePreprocess, ImagePostprocess, SlideWindowOld and
+ * SlideWindowNew drive it (R/swf/swf_image.cpp:27-62, 115-127, 313-320), for n_streams independent windows whose track table stays on
+ * the device.  It consumes swf_tracker_device_frame and produces the inputs of swf_pnp_frame_batch, swf_triangulate_batch
+ * and the flat window's lm / proj_idx / proj_uv.  Scope: the reference's compiled default, USE_INVERSE_DEPTH 0, USE_STEREO 0,
+ * FEATURE_CONTINUE 2.  Every operation is asynchronous on the table's stream, handles all streams in one call with one workgroup per
+ * stream, and does not synchronise, allocate or copy from the device; the number of launches depends on the operation alone (given
+ * with each).  Arrays are host memory, or device memory with on_device; tic, ric (row-major), pbg and mode are always host memory.
+ * State per stream: n_frames (the reference's image_count) and a list of at most feat_cap features IN THE REFERENCE'S LIST ORDER
+ * (insertion order, every erase a stable compaction; not sorted by id).  Per feature: id, start_frame, n_obs, valid, solve_flag,
+ * idepth, world[3] and up to `window` observations, each the tracker's 7-vector x y z u v vx vy with an in_problem bit.
+ * endFrame = start_frame + n_obs - 1.
+ *
+ * 1 swf_ftable_add_frame — addFeatureCheckParallax (:40-77), then removeOut (:418-425).  first [n_streams + 1], ids, obs [..][7] are
+ *   what swf_tracker_device_frame returns.  image_index = n_frames.  The frame's points are taken in ascending id (the reference
+ *   iterates a std::map; the tracker's frame is not sorted).  A found id appends its observation (in_problem clear), counts in
+ *   last_track_num and, when n_obs >= long_len after the append, in long_track_num.  An id not found is appended at the end of the
+ *   list with start_frame = image_index, valid = 0, solve_flag = 0, idepth = 0, world = 0 and counts in new_feature_num.
+ *   keyframe = image_index < 2 || last_track_num < min_track || long_track_num < min_long || new_feature_num > new_ratio * last_track_num.
+ *   Then n_frames += 1, then every feature with endFrame != n_frames - 1 && n_obs < feature_continue is erased.  counts: KEYFRAME,
+ *   LAST_TRACK, LONG_TRACK, NEW, ERASED, INFO.  Info bits: SWF_FTABLE_WINDOW_FULL (n_frames == window already) and SWF_FTABLE_BAD_FRAME
+ *   (an id twice in the frame, more than frame_cap points, offsets that are negative or decreasing, a non-finite observation): the
+ *   stream is left exactly as it was, n_frames included, its counters 0.  SWF_FTABLE_TABLE_FULL: the j-th new id, ascending, is taken
+ *   while (features before the call) + j < feat_cap; the others are dropped and not counted — a declared difference.   1 launch.
+ * 2 swf_ftable_pnp_points — the gather of initFramePoseByPnP (:207-228, world-point branch) with frameCnt = n_frames - 1: the valid
+ *   features with n_obs >= frameCnt - start_frame + 1, in list order, give world and x, y of the observation at frameCnt - start_frame.
+ *   The three out-pointers receive device arrays in swf_pnp_frame_batch's first / pts_w / pts_uv layout.  n_frames < 2: an empty
+ *   range.   2 launches.
+ * 3 swf_ftable_triangulate — triangulate (:245-316), the branch every feature with !valid && n_obs > 1 takes.  Ps [n_streams][window][3],
+ *   Rs [..][9] row-major by image frame.  A gather kernel writes start (s * window + start_frame, or -1 for a slot that is not to be
+ *   triangulated), pt0, pt1 for all n_streams * feat_cap slots, swf_triangulate_batch runs over them on device memory, a scatter
+ *   kernel takes the rows whose depth is not the -1 sentinel: idepth = 1 / depth, world, valid = 1.  Bit-identical to
+ *   swf_triangulate_batch on the same inputs.  The stereo branch and the N-view SVD (unreachable for feature_continue >= 2) are not
+ *   covered.   3 launches.
+ * 4 swf_ftable_list — AddFeature2Problem (R/swf/swf_image.cpp:65-114, world-point branch) as data: the features with
+ *   n_obs >= feature_continue in list order, their observations in frame order from start_frame.  Packed per stream behind lm_first /
+ *   proj_first [n_streams + 1]: lm_id, lm_world [..][3], lm_start, lm_nobs, lm_valid; proj_frame, proj_lm (an index into the stream's
+ *   listed landmarks), proj_uv [..][2] (x, y), proj_new (1 when in_problem was clear).  The call sets in_problem on everything it
+ *   lists and remembers the stream's landmark count.  counts: N_LISTED, N_PROJ.   2 launches.
+ * 5 swf_ftable_set_solved — the landmark tail of Double2Vector (R/swf/swf.cpp:214-228) and the verdict of OutliersRejection.
+ *   lm_world [..][3] behind lm_first, in the order of the last listing, is written to world; pts_cj = ric^T (Rs[start]^T (world - Ps[start])
+ *   + pbg - tic), idepth = 1 / pts_cj.z, solve_flag = idepth < 0 ? 2 : 1.  A non-null flags [..] (what swf_batch_get_feature_check
+ *   returns) with SWF_FEAT_OUTLIER or SWF_FEAT_NEG_DEPTH set makes solve_flag 2.  A stream whose features with n_obs >= feature_continue,
+ *   or whose lm_first range, do not number what its last listing did sets SWF_FTABLE_STALE_LIST and is left untouched.   1 launch.
+ * 6 swf_ftable_remove_failures — removeFailures (:122-139): the features with solve_flag == 2 are erased; the out-pointers receive
+ *   device first [n_streams + 1] / ids of the erased, packed, in list order.  swf_ftable_removed downloads them for
+ *   swf_tracker_remove_ids.  counts: ERASED.   2 launches.
+ * 7 swf_ftable_check_parallax — CheckParallax(n_frames - 1) with compensatedParallax2 (:81-101, 469-498), idx = n_frames - 1: over the
+ *   features with start_frame <= idx - 2 && endFrame >= idx - 1, sequentially in list order, term = sqrt(du du + dv dv),
+ *   du = x_i / z_i - x_j, dv = y_i / z_i - y_j, i and j the observations of frames idx - 2 and idx - 1.  counts: PARALLAX_NUM,
+ *   KEYFRAME = num == 0 || sum / num >= min_parallax; parallax [n_streams] = sum / num * focal (0 for num == 0).   1 launch.
+ * 8 swf_ftable_slide — mode [n_streams]: 0 leaves the stream alone.  1 is removeBack (:362-391): start_frame != 0 decrements it;
+ *   otherwise pts_cj = ric^T (R1^T (world - P1) + pbg - tic), idepth = 1 / pts_cj.z and observation 0 is erased.  2 is
+ *   removeFront(n_frames - 1) (:393-416), literally: start_frame == n_frames - 1 decrements it, otherwise a feature with
+ *   endFrame >= n_frames - 2 loses observation j = n_frames - 2 - start_frame (j == 0 included).  A feature left with no observation is
+ *   erased (the reference asserts there: a declared difference, the release build's behaviour).  Both then set n_frames -= 1 and clear
+ *   in_problem on every observation of a feature with n_obs < feature_continue (removeOut2's world-point effect, :427-447).  P1 [n_streams][3],
+ *   R1 [..][9]; P0, R0 are the reference's arguments, unread in world-point mode, and may be null.  Mode 1 or 2 with n_frames < 2,
+ *   or another mode: SWF_FTABLE_BAD_SLIDE, nothing done.  counts: ERASED, INFO.   1 launch.
+ * 9 swf_ftable_create allocates everything.  swf_ftable_download synchronises and copies the whole state in capacity layout:
+ *   n_frames, n_feat [n_streams]; id, start_frame, n_obs, valid, solve_flag, idepth [n_streams][feat_cap]; world [..][3];
+ *   obs [..][window][7]; in_problem [..][window]; any pointer may be null.  swf_ftable_counts synchronises and copies counts
+ *   [n_streams][SWF_FTABLE_NCOUNT] and parallax [n_streams]; every operation overwrites the words named with it, INFO included.
+ *   swf_ftable_clear is ClearState with n_frames = 0.
+ * Refused before the device is touched: null pointers, non-finite options: SWF_E_INVALID; n_streams outside 1 .. 65535, window outside
+ * 3 .. 32, feat_cap outside 1 .. 65536, frame_cap outside 1 .. SWF_PNP_NMAX, feature_continue outside 2 .. window: SWF_E_UNSUPPORTED; a
+ * host-memory first that is negative or decreasing: SWF_E_INVALID.
+ * A stream's result does not depend on the other streams, and a rerun from the same state gives the same bits.  Declared differences:
+ * TABLE_FULL, the erase where the reference asserts, world-point mode only. */
+typedef struct swf_ftable swf_ftable;
+typedef struct swf_ftable_options {    /* swf_ftable_default_options fills the reference's values */
+    int32_t window, feat_cap, frame_cap;            /* FEATURE_WINDOW_SIZE + 1 = 11, 4096, the tracker's max_cnt 350 */
+    int32_t feature_continue, min_track, min_long, long_len;   /* 2, 20, 40, 4 */
+    double  new_ratio, min_parallax, focal, init_depth;        /* 0.5, keyframe_parallax / FOCAL_LENGTH = 10 / 1000, 1000, 5.0 */
+} swf_ftable_options;
+typedef struct swf_ftable_listing {    /* device pointers, valid until the next swf_ftable_list */
+    const int32_t* lm_first; const int32_t* proj_first;
+    const int32_t* lm_id; const double* lm_world; const int32_t* lm_start; const int32_t* lm_nobs; const int32_t* lm_valid;
+    const int32_t* proj_frame; const int32_t* proj_lm; const double* proj_uv; const int32_t* proj_new;
+} swf_ftable_listing;
+enum { SWF_FTABLE_WINDOW_FULL = 1, SWF_FTABLE_TABLE_FULL = 2, SWF_FTABLE_BAD_FRAME = 4, SWF_FTABLE_STALE_LIST = 8, SWF_FTABLE_BAD_SLIDE = 16 };
+enum { SWF_FTABLE_C_KEYFRAME = 0, SWF_FTABLE_C_LAST_TRACK = 1, SWF_FTABLE_C_LONG_TRACK = 2, SWF_FTABLE_C_NEW = 3, SWF_FTABLE_C_ERASED = 4,
+       SWF_FTABLE_C_INFO = 5, SWF_FTABLE_C_PARALLAX_NUM = 6, SWF_FTABLE_C_N_LISTED = 7, SWF_FTABLE_C_N_PROJ = 8, SWF_FTABLE_C_N_PNP = 9 };
+#define SWF_FTABLE_NCOUNT 10
+void swf_ftable_default_options(swf_ftable_options*);
+int swf_ftable_create(int32_t n_streams, const swf_ftable_options* opt, void* stream, swf_ftable** out);
+int swf_ftable_add_frame(swf_ftable* t, const int32_t* first, const int32_t* ids, const double* obs, int32_t on_device);
+int swf_ftable_pnp_points(swf_ftable* t, const int32_t** first_out, const double** pts_w, const double** pts_uv);
+int swf_ftable_triangulate(swf_ftable* t, const double* Ps, const double* Rs, const double tic[3], const double ric[9], const double pbg[3],
+                           int32_t on_device);
+int swf_ftable_list(swf_ftable* t, swf_ftable_listing* out);
+int swf_ftable_set_solved(swf_ftable* t, const int32_t* lm_first, const double* lm_world, const uint8_t* flags /* or null */,
+                          const double* Ps, const double* Rs, const double tic[3], const double ric[9], const double pbg[3], int32_t on_device);
+int swf_ftable_remove_failures(swf_ftable* t, const int32_t** first_out, const int32_t** ids_out);
+int swf_ftable_removed(swf_ftable* t, int32_t* first /* host, [n_streams + 1] */, int32_t* ids /* host, up to n_streams * feat_cap */);
+int swf_ftable_check_parallax(swf_ftable* t);
+int swf_ftable_slide(swf_ftable* t, const int32_t* mode /* host */, const double* P0, const double* R0, const double* P1, const double* R1,
+                     const double tic[3], const double ric[9], const double pbg[3], int32_t on_device);
+int swf_ftable_download(swf_ftable* t, int32_t* n_frames, int32_t* n_feat, int32_t* id, int32_t* start_frame, int32_t* n_obs, int32_t* valid,
+                        int32_t* solve_flag, double* idepth, double* world, double* obs, int32_t* in_problem);
+int swf_ftable_counts(swf_ftable* t, int32_t* counts /* [n_streams][SWF_FTABLE_NCOUNT] */, double* parallax /* [n_streams] */);
+int swf_ftable_fetch(swf_ftable* t, void* dst, const void* device_src, uint64_t bytes);   /* synchronise, then copy a device array out */
+int swf_ftable_sync(swf_ftable* t);
+int swf_ftable_clear(swf_ftable* t);
+int swf_ftable_destroy(swf_ftable* t);
+
 /* Input producer: two-view landmark triangulation for a batch of features — FeatureManager::triangulate, the branch every
  * feature with >= 2 observations takes (R/feature/feature_manager.cpp:285-316), with triangulatePoint (:148-161).
  *   Ps [n_frames][3], Rs [n_frames][9] (row-major)  frame positions / rotations as the reference passes them

@@ -69,6 +69,10 @@ EXPORTED = [
     "swf_gftt_detect_batch", "swf_gftt_workspace_bytes",
     "swf_tracker_default_options", "swf_tracker_create", "swf_tracker_track", "swf_tracker_remove_ids", "swf_tracker_download",
     "swf_tracker_device_frame", "swf_tracker_sync", "swf_tracker_destroy",
+    "swf_ftable_default_options", "swf_ftable_create", "swf_ftable_add_frame", "swf_ftable_pnp_points", "swf_ftable_triangulate",
+    "swf_ftable_list", "swf_ftable_set_solved", "swf_ftable_remove_failures", "swf_ftable_removed", "swf_ftable_check_parallax",
+    "swf_ftable_slide", "swf_ftable_download", "swf_ftable_counts", "swf_ftable_fetch", "swf_ftable_sync", "swf_ftable_clear",
+    "swf_ftable_destroy",
 ]
 
 
@@ -1272,6 +1276,209 @@ class Tracker:
         p = [C.c_void_p() for _ in range(5)]
         _chk(lib().swf_tracker_device_frame(self._h, *[C.byref(v) for v in p]), "swf_tracker_device_frame")
         return dict(zip(("first", "ids", "track_cnt", "px", "obs"), [v.value for v in p]))
+
+
+FTABLE_WINDOW_FULL, FTABLE_TABLE_FULL, FTABLE_BAD_FRAME, FTABLE_STALE_LIST, FTABLE_BAD_SLIDE = 1, 2, 4, 8, 16
+FTABLE_NCOUNT = 10
+FTABLE_COUNTS = ("keyframe", "last_track", "long_track", "new", "erased", "info", "parallax_num", "n_listed", "n_proj", "n_pnp")
+FTABLE_LISTING = ("lm_first", "proj_first", "lm_id", "lm_world", "lm_start", "lm_nobs", "lm_valid", "proj_frame", "proj_lm", "proj_uv", "proj_new")
+
+
+class FtableOptionsC(C.Structure):
+    """swf_ftable_options of include/swf_solver.h"""
+    _fields_ = [("window", C.c_int32), ("feat_cap", C.c_int32), ("frame_cap", C.c_int32),
+                ("feature_continue", C.c_int32), ("min_track", C.c_int32), ("min_long", C.c_int32), ("long_len", C.c_int32),
+                ("new_ratio", C.c_double), ("min_parallax", C.c_double), ("focal", C.c_double), ("init_depth", C.c_double)]
+
+
+class FtableListingC(C.Structure):
+    """swf_ftable_listing of include/swf_solver.h: device addresses"""
+    _fields_ = [(k, C.c_void_p) for k in FTABLE_LISTING]
+
+
+def ftable_options(**options):
+    """the reference's options (swf_ftable_default_options) with the given fields replaced"""
+    o = FtableOptionsC()
+    lib().swf_ftable_default_options(C.byref(o))
+    names = {f[0] for f in FtableOptionsC._fields_}
+    for k, v in options.items():
+        if k not in names:
+            raise SwfError("FeatureTable: unknown option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+class FeatureTable:
+    """FeatureManager for n_streams windows whose track table stays on the device (swf_ftable_*); the options are the
+    fields of swf_ftable_options.  Every operation enqueues and returns at once; the methods that return arrays wait for them.
+    Poses are Ps [n_streams][window][3], Rs [n_streams][window][3][3] by image frame; tic [3], ric [3][3], pbg [3]."""
+
+    def __init__(self, n_streams, stream=None, **options):
+        self._h = C.c_void_p()
+        self.n_streams = int(n_streams)
+        self.opt = ftable_options(**options)
+        _chk(lib().swf_ftable_create(C.c_int32(n_streams), C.byref(self.opt), C.c_void_p(stream), C.byref(self._h)), "swf_ftable_create")
+
+    def close(self):
+        if self._h:
+            lib().swf_ftable_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _f64(a, shape=None):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        return a if shape is None else a.reshape(shape)
+
+    def _ext(self, tic, ric, pbg):
+        t, r, p = self._f64(tic, 3), self._f64(ric, 9), self._f64(pbg, 3)
+        return t, r, p, (t.ctypes.data_as(_pd), r.ctypes.data_as(_pd), p.ctypes.data_as(_pd))
+
+    def _poses(self, Ps, Rs, per):
+        return self._f64(Ps, (self.n_streams * per, 3)), self._f64(Rs, (self.n_streams * per, 9))
+
+    def _pack(self, per, width, dtype, what):
+        if len(per) != self.n_streams:
+            raise SwfError("FeatureTable.%s: %d arrays for %d streams" % (what, len(per), self.n_streams))
+        rows = [np.asarray(a, dtype).reshape((-1,) + width) for a in per]
+        first = np.concatenate([[0], np.cumsum([a.shape[0] for a in rows])]).astype(np.int32)
+        flat = np.ascontiguousarray(np.concatenate(rows + [np.zeros((1,) + width, dtype)]))
+        return first, flat
+
+    def _fetch(self, addr, shape, dtype):
+        out = np.zeros(shape, dtype)
+        if out.nbytes:
+            _chk(lib().swf_ftable_fetch(self._h, C.c_void_p(out.ctypes.data), C.c_void_p(addr), C.c_uint64(out.nbytes)), "swf_ftable_fetch")
+        return out
+
+    def add_frame(self, ids, obs):
+        """addFeatureCheckParallax + removeOut: one id array [n] and one obs array [n][7] per stream, host memory"""
+        first, fi = self._pack(ids, (), np.int32, "add_frame")
+        first_o, fo = self._pack(obs, (7,), np.float64, "add_frame")
+        if not np.array_equal(first, first_o):
+            raise SwfError("FeatureTable.add_frame: ids and obs disagree on the number of points")
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_ftable_add_frame(self._h, first.ctypes.data_as(pi), fi.ctypes.data_as(pi), fo.ctypes.data_as(_pd), C.c_int32(0)),
+             "swf_ftable_add_frame")
+
+    def add_frame_device(self, d_first, d_ids, d_obs):
+        """add_frame for a frame that is device memory already: the first, ids, obs of Tracker.device_frame()"""
+        _chk(lib().swf_ftable_add_frame(self._h, C.c_void_p(d_first), C.c_void_p(d_ids), C.c_void_p(d_obs), C.c_int32(1)), "swf_ftable_add_frame")
+
+    def pnp_points_device(self):
+        """the device addresses of swf_pnp_frame_batch's first, pts_w, pts_uv"""
+        p = [C.c_void_p() for _ in range(3)]
+        _chk(lib().swf_ftable_pnp_points(self._h, *[C.byref(v) for v in p]), "swf_ftable_pnp_points")
+        return dict(zip(("first", "pts_w", "pts_uv"), [v.value for v in p]))
+
+    def pnp_points(self):
+        """per stream (pts_w [n][3], pts_uv [n][2]): the gather of initFramePoseByPnP"""
+        d = self.pnp_points_device()
+        first = self._fetch(d["first"], self.n_streams + 1, np.int32)
+        w, uv = self._fetch(d["pts_w"], (int(first[-1]), 3), np.float64), self._fetch(d["pts_uv"], (int(first[-1]), 2), np.float64)
+        return [(w[first[s]:first[s + 1]].copy(), uv[first[s]:first[s + 1]].copy()) for s in range(self.n_streams)]
+
+    def triangulate(self, Ps, Rs, tic, ric, pbg):
+        P, R = self._poses(Ps, Rs, self.opt.window)
+        _, _, _, e = self._ext(tic, ric, pbg)
+        _chk(lib().swf_ftable_triangulate(self._h, P.ctypes.data_as(_pd), R.ctypes.data_as(_pd), e[0], e[1], e[2], C.c_int32(0)), "swf_ftable_triangulate")
+
+    def list_device(self):
+        """the device addresses of the listing (FTABLE_LISTING names them)"""
+        L = FtableListingC()
+        _chk(lib().swf_ftable_list(self._h, C.byref(L)), "swf_ftable_list")
+        return {k: getattr(L, k) for k in FTABLE_LISTING}
+
+    def list(self):
+        """AddFeature2Problem as data: per stream a dict of lm_id, lm_world [..][3], lm_start, lm_nobs, lm_valid and proj_frame,
+        proj_lm, proj_uv [..][2], proj_new"""
+        d = self.list_device()
+        lf, pf = self._fetch(d["lm_first"], self.n_streams + 1, np.int32), self._fetch(d["proj_first"], self.n_streams + 1, np.int32)
+        nl, npj = int(lf[-1]), int(pf[-1])
+        a = dict(lm_id=self._fetch(d["lm_id"], nl, np.int32), lm_world=self._fetch(d["lm_world"], (nl, 3), np.float64),
+                 lm_start=self._fetch(d["lm_start"], nl, np.int32), lm_nobs=self._fetch(d["lm_nobs"], nl, np.int32),
+                 lm_valid=self._fetch(d["lm_valid"], nl, np.int32), proj_frame=self._fetch(d["proj_frame"], npj, np.int32),
+                 proj_lm=self._fetch(d["proj_lm"], npj, np.int32), proj_uv=self._fetch(d["proj_uv"], (npj, 2), np.float64),
+                 proj_new=self._fetch(d["proj_new"], npj, np.int32))
+        return [{k: (v[lf[s]:lf[s + 1]] if k.startswith("lm_") else v[pf[s]:pf[s + 1]]).copy() for k, v in a.items()}
+                for s in range(self.n_streams)]
+
+    def set_solved(self, lm_world, flags, Ps, Rs, tic, ric, pbg):
+        """the solved world points (one [n][3] array per stream, in the order of the last list()) and, unless None, the feature
+        check's flags (one [n] uint8 array per stream)"""
+        first, w = self._pack(lm_world, (3,), np.float64, "set_solved")
+        fl = None
+        if flags is not None:
+            first_f, fl = self._pack(flags, (), np.uint8, "set_solved")
+            if not np.array_equal(first, first_f):
+                raise SwfError("FeatureTable.set_solved: lm_world and flags disagree on the number of landmarks")
+        P, R = self._poses(Ps, Rs, self.opt.window)
+        _, _, _, e = self._ext(tic, ric, pbg)
+        _chk(lib().swf_ftable_set_solved(self._h, first.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(_pd),
+                                         fl.ctypes.data_as(C.POINTER(C.c_uint8)) if fl is not None else None,
+                                         P.ctypes.data_as(_pd), R.ctypes.data_as(_pd), e[0], e[1], e[2], C.c_int32(0)), "swf_ftable_set_solved")
+
+    def remove_failures(self, fetch=True):
+        """removeFailures; -> the erased ids per stream, the argument of Tracker.remove_ids (None without fetch)"""
+        _chk(lib().swf_ftable_remove_failures(self._h, None, None), "swf_ftable_remove_failures")
+        if not fetch:
+            return None
+        first, ids = np.zeros(self.n_streams + 1, np.int32), np.zeros(self.n_streams * self.opt.feat_cap, np.int32)
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_ftable_removed(self._h, first.ctypes.data_as(pi), ids.ctypes.data_as(pi)), "swf_ftable_removed")
+        return [ids[first[s]:first[s + 1]].copy() for s in range(self.n_streams)]
+
+    def check_parallax(self):
+        _chk(lib().swf_ftable_check_parallax(self._h), "swf_ftable_check_parallax")
+
+    def slide(self, mode, P1, R1, tic, ric, pbg):
+        """mode [n_streams]: 0 nothing, 1 removeBack with the new oldest frame's P1 [n_streams][3], R1 [n_streams][3][3], 2 removeFront"""
+        m = np.ascontiguousarray(np.asarray(mode, np.int32).reshape(self.n_streams))
+        P, R = self._poses(P1, R1, 1)
+        _, _, _, e = self._ext(tic, ric, pbg)
+        _chk(lib().swf_ftable_slide(self._h, m.ctypes.data_as(C.POINTER(C.c_int32)), None, None, P.ctypes.data_as(_pd), R.ctypes.data_as(_pd),
+                                    e[0], e[1], e[2], C.c_int32(0)), "swf_ftable_slide")
+
+    def sync(self):
+        _chk(lib().swf_ftable_sync(self._h), "swf_ftable_sync")
+
+    def clear(self):
+        _chk(lib().swf_ftable_clear(self._h), "swf_ftable_clear")
+
+    def counts(self):
+        """(counts [n_streams][FTABLE_NCOUNT] (FTABLE_COUNTS names them), parallax [n_streams])"""
+        c, p = np.zeros((self.n_streams, FTABLE_NCOUNT), np.int32), np.zeros(self.n_streams)
+        _chk(lib().swf_ftable_counts(self._h, c.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(_pd)), "swf_ftable_counts")
+        return c, p
+
+    def state(self):
+        """the whole table: per stream a dict of n_frames and, for its features in list order, id, start_frame, n_obs, valid,
+        solve_flag, idepth, world [..][3], obs [..][window][7], in_problem [..][window]; the slots past n_obs are zeroed"""
+        ns, F, W = self.n_streams, self.opt.feat_cap, self.opt.window
+        nf, n = np.zeros(ns, np.int32), np.zeros(ns, np.int32)
+        i32 = {k: np.zeros((ns, F), np.int32) for k in ("id", "start_frame", "n_obs", "valid", "solve_flag")}
+        idepth, world, obs, inp = np.zeros((ns, F)), np.zeros((ns, F, 3)), np.zeros((ns, F, W, 7)), np.zeros((ns, F, W), np.int32)
+        pi = C.POINTER(C.c_int32)
+        _chk(lib().swf_ftable_download(self._h, nf.ctypes.data_as(pi), n.ctypes.data_as(pi), i32["id"].ctypes.data_as(pi),
+                                       i32["start_frame"].ctypes.data_as(pi), i32["n_obs"].ctypes.data_as(pi), i32["valid"].ctypes.data_as(pi),
+                                       i32["solve_flag"].ctypes.data_as(pi), idepth.ctypes.data_as(_pd), world.ctypes.data_as(_pd),
+                                       obs.ctypes.data_as(_pd), inp.ctypes.data_as(pi)), "swf_ftable_download")
+        out = []
+        for s in range(ns):
+            m = int(n[s])
+            d = {k: v[s, :m].copy() for k, v in i32.items()}
+            dead = np.arange(W)[None, :] >= d["n_obs"][:, None]
+            o, ip = obs[s, :m].copy(), inp[s, :m].copy()
+            o[dead] = 0.0
+            ip[dead] = 0
+            d.update(n_frames=int(nf[s]), idepth=idepth[s, :m].copy(), world=world[s, :m].copy(), obs=o, in_problem=ip)
+            out.append(d)
+        return out
 
 
 def triangulate_batch(Ps, Rs, tic, ric, pbg, start_frame, pt0, pt1, init_depth=5.0):
