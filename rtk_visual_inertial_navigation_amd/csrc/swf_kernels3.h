@@ -25,7 +25,8 @@
 // and L_nn with it.  This kernel steps in for exactly those windows (WinState::chol_fail): a right-looking Cholesky of the
 // first m columns only, in the window's (now free) L buffer, leaves the Schur complement A and the reduced right-hand side b
 // in the trailing block; a diagonally pivoted outer-product Cholesky of A then yields rows v_r with sum_r v_r v_r^T = A up to
-// the pivots it drops (rank-revealing: it stops at pivots below 1e-14 of the largest).  k_marginalize takes M = [v_r] and b
+// the pivots it drops (rank-revealing and scale-invariant: an index is null once its running diagonal is at most 1e-14 of its own
+// A_ii, swf_rootdev.h).  k_marginalize takes M = [v_r] and b
 // from here instead of L_nn / y_n.
 // A singular S_mm — a marginalised state nothing constrains, or a direction of the marginalised block only a combination of
 // which is observed — is business as usual in the reference too: UpdateSchur PSEUDO-inverts S_mm (eigenvalues <= 1e-8 dropped,

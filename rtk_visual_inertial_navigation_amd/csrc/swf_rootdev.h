@@ -11,7 +11,7 @@
 #define Mc(c, r) Mm[(c) * n + (r)]
 #define RS_NB 16
 // Diagonally pivoted Cholesky of the n x n matrix A (full symmetric, ld = n; read only), 16 pivots at a time, by one 1024-thread
-// workgroup: rows v_r of V (ld = n) with sum_r v_r v_r^T = A up to the pivots it drops (it stops at pivots below 1e-14 of the largest;
+// workgroup: rows v_r of V (ld = n) with sum_r v_r v_r^T = A up to the pivots it drops (the stopping rules: drop_abs below;
 // the remaining rows are zero).  LEFT-LOOKING by blocks: a block starts from a POOL of candidates, the (up to) 24 largest entries of
 // the running diagonal; their rows of the Schur complement, A[p, :] - sum_r v_r[:] v_r[p] over all rows so far, are formed in LDS in one
 // pass over V; the block's (up to) 16 pivots are then taken from the pool in the order the running diagonal dictates (it is kept up to
@@ -29,7 +29,12 @@
 #define RS_POOL 24                        // candidate rows held per block (16 of them at most become pivots)
 #define RS_GONE (-1e300)
 template <bool INPLACE>
-// drop_abs: the stopping rule.  The rank-deficient tails pass 0: a pivot below 1e-14 of the largest ends the factorisation (rank-revealing).
+// drop_abs: the stopping rule.  The rank-deficient tails pass 0: the rank-revealing rule, which is SCALE-INVARIANT — an index is
+// numerically null once its running diagonal is at most 1e-14 of ITS OWN original A_ii (never a pivot, dropped with its pool), and the
+// factorisation ends when no index is left.  (Until this rule the cut was 1e-14 of the LARGEST diagonal entry: with a state of information
+// 1e10 in the tail it sat at 1e-4, and decoupled states of information 9e-6 .. 9e-8, which the reference's absolute eigenvalue threshold
+// of 1e-8 keeps, came out of k_marg_rescue with a null row — tests/test_eigroot_componentwise.py, rescue_weak.)  What it leaves out is a
+// positive semi-definite remainder with diagonal <= 1e-14 A_ii, so |remainder_ij| <= 1e-14 sqrt(A_ii A_jj).
 // The preconditioner of a HEALTHY window (its Cholesky went through: A is numerically definite) passes eps / (16 n), eps = the caller's
 // eigenvalue threshold (the reference's 1e-8, R/factor/marginalization_factor.cpp:463-470): there the relative cut alone would drop
 // whole directions the reference keeps — with diag(A) ~ 1e10 it sits at 1e-4, far above eps — whereas a factorisation that ends at a
@@ -37,6 +42,7 @@ template <bool INPLACE>
 __device__ __forceinline__ void d_pivoted_chol(const double* A, double* V, double* VT, double* Rb, double* dg, double* stg, const int rc, const int n, const double drop_abs = 0.0) {
     __shared__ int cid[RS_POOL];                          // the block's candidates (indices)
     __shared__ double cdg[RS_POOL];                       // their running diagonal entries; -2 once taken, -1 for an empty slot
+    __shared__ double cthr[RS_POOL];                      // drop_abs == 0: 1e-14 of their own original diagonal entries (at or below it: numerically null)
     __shared__ int ncand_s;
     __shared__ double d0_s;
     const int tid = threadIdx.x;
@@ -60,7 +66,7 @@ __device__ __forceinline__ void d_pivoted_chol(const double* A, double* V, doubl
     while (r0 < n && !stop) {
         double* R = INPLACE ? V + (size_t)r0 * n : Rb;        // (a compile-time choice: the pointer keeps its address space, LDS either way)
         // ---- the block's candidate pool: the largest entries of the running diagonal, by rank (ties: the smaller index first)
-        if (tid < RS_POOL) { cid[tid] = -1; cdg[tid] = -1.0; }
+        if (tid < RS_POOL) { cid[tid] = -1; cdg[tid] = -1.0; cthr[tid] = 0.0; }
         if (tid == 0) ncand_s = 0;
         __syncthreads();
         int myslot = -1;
@@ -79,7 +85,7 @@ __device__ __forceinline__ void d_pivoted_chol(const double* A, double* V, doubl
         __syncthreads();
         if (act && dg[i] > 0.5 * RS_GONE) {
             const int rank = rk[i];
-            if (rank < pool) { myslot = rank; cid[rank] = i; cdg[rank] = dg[i]; atomicAdd(&ncand_s, 1); }
+            if (rank < pool) { myslot = rank; cid[rank] = i; cdg[rank] = dg[i]; if (!(drop_abs > 0.0)) cthr[rank] = fmax(0.0, 1e-14 * A[(size_t)i * n + i]); atomicAdd(&ncand_s, 1); }
         }
         __syncthreads();
         if (INPLACE && act && 2 * i < n + 1) R[i] = 0.0;      // (the rank counters sat in a row of V)
@@ -141,13 +147,16 @@ __device__ __forceinline__ void d_pivoted_chol(const double* A, double* V, doubl
             // (every wave, redundantly — no broadcast step — but lane-parallel: most of the 16 waves have no index to work on, and what
             // they issue here competes with the waves that do.  Lane c holds candidate c; the first lane holding the maximum wins.)
             const int ln = tid & 63;
-            const double cv = ln < RS_POOL ? cdg[ln] : -3.0;
+            // (a candidate at or below its cut is never a pivot.  With the one cut of drop_abs > 0 that is the test of the largest one)
+            const double cv = ln < RS_POOL && cdg[ln] > (drop_abs > 0.0 ? thr : cthr[ln]) ? cdg[ln] : -3.0;
             const double m16 = grp16_max(cv);
             const double bv = fmax(rows_lane(m16, 0), rows_lane(m16, 16));
             const unsigned long long hit = __builtin_amdgcn_ballot_w64(cv == bv);
             int bc = hit ? __builtin_ctzll(hit) : -1;
-            const int ok = (int)(bc >= 0 && bv > thr && bv > 0.0);      // uniform
-            if (!ok) { if (sblk == 0) stop = true; break; }      // numerically zero; the largest of all: rank reached
+            const int ok = (int)(bc >= 0 && bv > 0.0);      // uniform
+            // no candidate left above its cut.  drop_abs > 0: the largest of all is numerically zero, rank reached.  drop_abs == 0: the
+            // pool holds null indices only; they are dropped below and the next pool may hold smaller indices that are not null on their own scale
+            if (!ok) { if (sblk == 0 && drop_abs > 0.0) stop = true; break; }
             const int p = __builtin_amdgcn_readfirstlane(cid[bc]); const double isq = rsqrt_nr(bv);
             // row of the pivot: its pool row minus the block's earlier rows (all requests before the first use); zero at eliminated indices
             if (act) {
@@ -171,7 +180,7 @@ __device__ __forceinline__ void d_pivoted_chol(const double* A, double* V, doubl
         }
         PCACC(2);
         // pool members that are numerically null by now (a running diagonal only shrinks) are dropped for good
-        if (act && myslot >= 0) { const double di = dg[i]; if (di > 0.5 * RS_GONE && !(di > thr)) dg[i] = RS_GONE; }
+        if (act && myslot >= 0) { const double di = dg[i]; if (di > 0.5 * RS_GONE && !(di > (drop_abs > 0.0 ? thr : cthr[myslot]))) dg[i] = RS_GONE; }
         if (INPLACE) {
             // the block's rows to the front of the pool's slots, in pivot order (row swaps inside LDS: thread i moves column i)
             for (int t = 0; t < nbk; t++) {
@@ -194,7 +203,7 @@ __device__ __forceinline__ void d_pivoted_chol(const double* A, double* V, doubl
             for (int t = 0; t < nbk; t++) { const double v = R[(size_t)slot_of(t) * n + i]; V[(size_t)(r0 + t) * n + i] = v; VT[(size_t)i * n + r0 + t] = v; }
         }
         r0 += nbk;
-        if (nbk == 0) stop = true;
+        if (nbk == 0 && drop_abs > 0.0) stop = true;      // (drop_abs == 0: every member of the pool was dropped above, the loop ends at an empty pool)
         __threadfence_block();
         __syncthreads();
         PCACC(3);
